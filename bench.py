@@ -5,9 +5,17 @@ matrix values + constant-source RHS (one fused kernel; the module's
 rhs.fill(0) + applyConstantSourceToRhs, modules/poisson/FemModule.cc:163-169),
 the penalty Dirichlet list (forced info/value, rhs = P g) and the forced
 values written into the CSR (the reference's K14/K8/K16/K19 sequence).
-Inputs (mesh, structure) are resident in HBM before the timed region.
-Afterwards a fixed number of Jacobi-PCG iterations on the assembled CSR is
-timed for the CG iter/s half of the metric.
+Inputs (mesh, structure) are resident in HBM before the timed region; they
+are generated from fixed seeds, identical from run to run.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, settles,
+warms up, times the K steps, writes the last step's outputs when
+--dump-outputs DIR is given (csr_values.npy, rhs.npy: dump_outputs()) and
+prints the result lines.  Everything else is behind --full: the same K steps
+before the settle (value_unsettled), a fixed number of Jacobi-PCG iterations on
+the assembled CSR timed for the CG iter/s half of the metric, the per-rank
+communication profile (N > 1), the side measurements and the CPU baselines
+below.
 
 Timing: before the W untimed warmup steps the step runs back to back for
 --settle-ms (150) of wall time, untimed, so the GPU clocks have left their
@@ -25,7 +33,7 @@ communication, the CG exchanges ghost values and sums dot products through
 RCCL (libafem's own communicator; torch.distributed/gloo is only the control
 plane: bootstrap of the RCCL id, barriers, max-over-ranks of the timings).
 
-Side measurements at N=1 (rank 0): C4 (Poisson-3D at 10^8 DoF on one GPU:
+Side measurements with --full at N=1 (rank 0): C4 (Poisson-3D at 10^8 DoF on one GPU:
 assembly + CG), C3 (block-3 elasticity), C5 (elastodynamics step), and the
 CPU baselines of BASELINE.md §4 (assembly cell loop, OpenMP Jacobi-PCG over 50
 fixed iterations, the C1 dense SequentialBasic end to end).
@@ -66,17 +74,30 @@ def parse(argv=None):
                          "size); strong: ONE n x n x n box cut into N z-slabs (C4, n = 463)")
     ap.add_argument("--n", type=int, default=None,
                     help="cells per unit length (default: weak 215 -> 10.08M DoF per GPU, strong 463 -> 99.9M DoF)")
-    ap.add_argument("--cg-iters", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also measure everything else: the same steps before the "
+                         "clock settle (value_unsettled), the CG iter/s half of the metric, the per-rank communication "
+                         "profile (N > 1), the side legs (--legs) and the CPU baselines.  Without it the run sets up, "
+                         "warms up, times the steps and prints the result line; --cg-iters, --legs, --no-extras, "
+                         "--no-cpu-baseline and the legs' sizes select among what --full adds and have no effect "
+                         "without it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (the CSR values and the RHS, "
+                         "penalty Dirichlet rows included) to DIR/<name>.npy as float64, at most 64 MB in all "
+                         "(larger arrays: a fixed seeded sample of their entries); the headline's outputs, so not "
+                         "with --no-headline")
+    ap.add_argument("--cg-iters", type=int, default=100,
+                    help="--full: the fixed number of Jacobi-PCG iterations timed for CG iter/s")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the CPU baselines (the oracle timed at the C2 size on the host cores, N = 1 only)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side measurements (N = 1 only anyway)")
+                    help="--full: skip the CPU baselines (the oracle timed at the C2 size on the host cores, N = 1 only)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the side measurements (N = 1 only anyway)")
     ap.add_argument("--legs", default="c4,c3,c2_generic,c2_arrays,c2_arrays_natural,unstructured,unstructured_solve,"
                                       "generic_unstructured,c5",
-                    help="the side measurements to run (comma list of c4, c3, c2_generic, c2_arrays, "
+                    help="--full: the side measurements to run (comma list of c4, c3, c2_generic, c2_arrays, "
                          "c2_arrays_natural, unstructured, unstructured_solve (the unstructured leg's system solved "
                          "by the Jacobi- and the AMG-PCG), generic_unstructured, c5)")
     ap.add_argument("--no-headline", action="store_true",
-                    help="N = 1: skip the headline C2 step (and the CPU baselines), run only --legs (per-leg "
+                    help="--full, N = 1: skip the headline C2 step (and the CPU baselines), run only --legs (per-leg "
                          "rocprofv3 runs, tools/profile_legs.sh)")
     ap.add_argument("--c3-n", type=int, default=170, help="C3 block-3 elasticity box (170 -> 5.0M nodes)")
     ap.add_argument("--c4-n", type=int, default=463, help="C4 Poisson box on one GPU (463 -> 99.9M DoF); 0: skip")
@@ -88,6 +109,12 @@ def parse(argv=None):
     ap.add_argument("--unstructured-levels", type=int, default=6,
                     help="refinements of L-shape-3D.msh for the unstructured leg (6 -> 12 M DoF); 0: skip")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.no_headline and not args.full:
+        ap.error("--no-headline runs the side legs only: they are part of --full")
+    if args.no_headline and args.dump_outputs:
+        ap.error("--dump-outputs writes the headline step's outputs: not with --no-headline")
     if args.n is None:
         args.n = 215 if args.scaling == "weak" else 463
     return args
@@ -181,6 +208,40 @@ def make_step(ctx, bsr, ls, bottom, dbottom):
         ls.applyBoundaryConditions()
 
     return step
+
+
+DUMP_SEED = 20250220
+DUMP_BUDGETS = {"csr_values": 32 << 20, "rhs": 16 << 20}  # bytes per array; 48 MB in all
+
+
+def dump_sample(a, max_bytes, seed=DUMP_SEED):
+    """`a` itself when it fits into max_bytes, else its entries at a fixed
+    seeded draw of sorted, distinct positions (the same positions for every
+    run with the same array length): the draw with repeats dropped, topped up
+    from further draws until it holds max_bytes of entries."""
+    k = max_bytes // a.itemsize
+    if a.size <= k:
+        return a
+    rng = np.random.default_rng(seed)
+    idx = np.unique(rng.integers(0, a.size, size=k))
+    while idx.size < k:
+        idx = np.unique(np.concatenate([idx, rng.integers(0, a.size, size=k - idx.size)]))
+    return a[idx]
+
+
+def dump_outputs(ctx, bsr, ls, out_dir, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed step holds after it -- the
+    CSR values (the penalty diagonal of the Dirichlet rows included) and the
+    RHS of the linear system -- copied to the host as they stand after the
+    last timed step and written as float64 .npy files (dump_sample of each;
+    N > 1: one file per rank, the byte budget shared among the ranks)."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    v = bsr.view()
+    arrays = {"csr_values": ctx.to_host(v.values, v.nnz_blocks * v.block_size ** 2, np.float64),
+              "rhs": ls.rhs_host()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), dump_sample(a, DUMP_BUDGETS[name] // world))
 
 
 def roofline(bsr, mesh, kernel_ms):
@@ -306,7 +367,7 @@ def compact_line(out):
     (kernel ms, frac, frac_traffic ...).  The full record is the preceding
     {"bench_detail": ...} line."""
     keys = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-            "vs_baseline", "dtype", "data")
+            "vs_baseline", "dtype", "data", "full")
     c = _pick(out, keys)
     cfg = out["config"]
     c["config"] = {"workload": cfg["workload"].split(",")[0], **_pick(cfg, ("n", "dof_total", "nnz_rank0",
@@ -1064,24 +1125,26 @@ def main():
     setup_s = time.perf_counter() - t_setup
     step = make_step(ctx, bsr, ls, bottom, dbottom)
 
-    # unsettled: W warmup steps and K timed steps right after the setup, before
-    # the clock-settle phase (the line reports both; the settled run
-    # below is `value`)
-    for _ in range(args.warmup):
-        step()
-    ctx.synchronize()
-    if dist:
-        dist.barrier()
-    ctx.synchronize()
-    t0 = time.perf_counter()
-    uslots = min(args.steps, 27)
-    for i in range(args.steps):
-        step(200 + 2 * i if i < uslots else None)
-    ctx.synchronize()
-    if dist:
-        dist.barrier()
-    elapsed_unsettled = time.perf_counter() - t0
-    kernel_ms_unsettled = [ctx.event_elapsed(200 + 2 * i, 201 + 2 * i) for i in range(uslots)]
+    # --full, unsettled: W warmup steps and K timed steps right after the setup,
+    # before the clock-settle phase (the line reports both; the
+    # settled run below is `value`)
+    elapsed_unsettled, kernel_ms_unsettled = None, None
+    if args.full:
+        for _ in range(args.warmup):
+            step()
+        ctx.synchronize()
+        if dist:
+            dist.barrier()
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        uslots = min(args.steps, 27)
+        for i in range(args.steps):
+            step(200 + 2 * i if i < uslots else None)
+        ctx.synchronize()
+        if dist:
+            dist.barrier()
+        elapsed_unsettled = time.perf_counter() - t0
+        kernel_ms_unsettled = [ctx.event_elapsed(200 + 2 * i, 201 + 2 * i) for i in range(uslots)]
 
     settle_steps = settle(ctx, step, args.settle_ms)
     for _ in range(args.warmup):
@@ -1103,9 +1166,9 @@ def main():
     if dist:
         import torch
 
-        t = torch.tensor([elapsed, elapsed_unsettled], dtype=torch.float64)
+        t = torch.tensor([elapsed, elapsed_unsettled or 0.0], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, elapsed_unsettled = float(t[0]), float(t[1])
+        elapsed, elapsed_unsettled = float(t[0]), float(t[1]) if args.full else None
         tot = torch.tensor([float(n_own)], dtype=torch.float64)
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         total_dof = float(tot[0])
@@ -1114,27 +1177,32 @@ def main():
     ms_per_step = elapsed * 1e3 / args.steps
     value = total_dof * args.steps / elapsed / 1e6
 
-    # ---- CG iter/s on the assembled system (fixed iteration count)
-    ls.setSolverOptions(fixed_iterations=args.cg_iters)
-    if dist:
-        dist.barrier()
-    ctx.synchronize()
-    t0 = time.perf_counter()
-    st = ls.solve()
-    ctx.synchronize()
-    cg_s_own = time.perf_counter() - t0
-    if dist:
-        dist.barrier()
-    cg_s = time.perf_counter() - t0
-    if dist:
-        import torch
+    if args.dump_outputs:
+        dump_outputs(ctx, bsr, ls, args.dump_outputs, rank, world)
 
-        t = torch.tensor([cg_s], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        cg_s = float(t[0])
-    cg_iter_per_s = args.cg_iters / cg_s
+    # ---- --full: CG iter/s on the assembled system (fixed iteration count)
+    st, cg_s, cg_iter_per_s = None, None, None
+    if args.full:
+        ls.setSolverOptions(fixed_iterations=args.cg_iters)
+        if dist:
+            dist.barrier()
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        st = ls.solve()
+        ctx.synchronize()
+        cg_s_own = time.perf_counter() - t0
+        if dist:
+            dist.barrier()
+        cg_s = time.perf_counter() - t0
+        if dist:
+            import torch
+
+            t = torch.tensor([cg_s], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            cg_s = float(t[0])
+        cg_iter_per_s = args.cg_iters / cg_s
     per_rank = None
-    if dist:
+    if dist and args.full:
         # where each rank's time goes: its assembly kernel time,
         # and a separate short PCG run with the loop's halo waits and scalar
         # all-reduces timed by HIP events on the context stream (outside the
@@ -1165,16 +1233,17 @@ def main():
         kmed = float(np.median(kernel_ms))
         rf = roofline(bsr, mesh, kmed)
         rf["kernel_ms_mean"] = round(float(np.mean(kernel_ms)), 4)
-        rf["kernel_ms_unsettled"] = round(float(np.median(kernel_ms_unsettled)), 4)
-        rf["frac_unsettled"] = round(rf["algorithmic_bytes_per_launch"] / (rf["kernel_ms_unsettled"] * 1e-3) / 1e9
-                                     / HBM_PEAK_GBS, 4)
+        if args.full:
+            rf["kernel_ms_unsettled"] = round(float(np.median(kernel_ms_unsettled)), 4)
+            rf["frac_unsettled"] = round(rf["algorithmic_bytes_per_launch"] / (rf["kernel_ms_unsettled"] * 1e-3)
+                                         / 1e9 / HBM_PEAK_GBS, 4)
         rf["traffic"] = None
         if world == 1:
             with_traffic(rf, "c2" if args.scaling == "weak" else "c4", n, kmed)
         extras = {}
         c2 = None
         if world == 1:
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 c2 = download_c2(ctx, mesh, bsr, ls, bottom)
             # free the headline's buffers before the large side legs
             ctx.free(dbottom)
@@ -1182,7 +1251,7 @@ def main():
             bsr.close()
             mesh.close()
             dbottom = None
-        legs = set() if args.no_extras or world > 1 else set(args.legs.split(","))
+        legs = set() if not args.full or args.no_extras or world > 1 else set(args.legs.split(","))
         if args.scaling == "strong" and n == args.c4_n:
             legs.discard("c4")
         extras = run_legs(ctx, af, args, legs)
@@ -1210,8 +1279,8 @@ def main():
             "settle_ms": args.settle_ms,
             "settle_steps": settle_steps,
             "ms_per_step": round(ms_per_step, 4),
-            "ms_per_step_unsettled": round(elapsed_unsettled * 1e3 / args.steps, 4),
-            "value_unsettled": round(total_dof * args.steps / elapsed_unsettled / 1e6, 3),
+            **({"ms_per_step_unsettled": round(elapsed_unsettled * 1e3 / args.steps, 4),
+                "value_unsettled": round(total_dof * args.steps / elapsed_unsettled / 1e6, 3)} if args.full else {}),
             "higher_is_better": True,
             "scaling": args.scaling,
             "vs_baseline": None,
@@ -1227,17 +1296,19 @@ def main():
                 "parallelism": f"z-slab x{world}, {'RCCL' if args.comm == 'rccl' else 'host-transport'} halo + all-reduce in CG",
             },
             "roofline": rf,
+            "full": args.full,
             "cpu_baseline": cpu,
-            "cg_iter_per_s": round(cg_iter_per_s, 2),
-            "cg_ms_per_iter": round(cg_s * 1e3 / args.cg_iters, 4),
-            "cg_roofline_frac": round(cg_bytes(nnz, n_own) * cg_iter_per_s / 1e9 / HBM_PEAK_GBS, 4),
-            "cg_device_ms": round(st["solve_ms"], 3), "cg_spmv": SPMV_KERNELS.get(st["spmv_kernel"]),
+            **({"cg_iter_per_s": round(cg_iter_per_s, 2),
+                "cg_ms_per_iter": round(cg_s * 1e3 / args.cg_iters, 4),
+                "cg_roofline_frac": round(cg_bytes(nnz, n_own) * cg_iter_per_s / 1e9 / HBM_PEAK_GBS, 4),
+                "cg_device_ms": round(st["solve_ms"], 3),
+                "cg_spmv": SPMV_KERNELS.get(st["spmv_kernel"])} if args.full else {}),
             "sparsity_ms": round(sparsity_ms, 1),
             "setup_s": round(setup_s, 2),
             **({"per_rank": per_rank} if per_rank else {}),
             **extras,
         }
-        if world == 1 and args.scaling == "weak":
+        if args.full and world == 1 and args.scaling == "weak":
             out.update(cg_traffic("c2_spmv", n, n_own, cg_iter_per_s))
         print(json.dumps({"bench_detail": out}), flush=True)
         print(json.dumps(compact_line(out)), flush=True)

@@ -79,3 +79,61 @@ def test_with_traffic_recomputes_from_the_profile():
     assert out["traffic_over_min"] == round(b / rf["bytes_kernel_min"], 3)
     none = bench.with_traffic(dict(rf), "no_such_leg", 215, 0.5)
     assert none["traffic"] is None and none["frac_traffic"] is None
+
+
+def test_plain_run_is_the_default_and_the_legs_need_full():
+    """--full is off by default (a plain run times the headline's steps and
+    nothing else); the leg-only mode belongs to --full."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--full", "--no-headline", "--legs", "c3"])
+    assert a.full and a.no_headline
+    assert bench.parse(["--full", "--dump-outputs", "d"]).dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse(["--no-headline"])
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse(["--full", "--no-headline", "--dump-outputs", "d"])
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs: an array within its byte budget is written whole, a
+    larger one as its entries at the same sorted seeded positions every time."""
+    import numpy as np
+
+    a = np.arange(1000, dtype=np.float64)
+    assert bench.dump_sample(a, 8000) is a
+    s = bench.dump_sample(a, 800)
+    assert s.dtype == np.float64 and s.nbytes == 800
+    assert np.array_equal(s, bench.dump_sample(a.copy(), 800))
+    assert np.all(np.diff(s) > 0)  # sorted, distinct positions
+    assert sum(bench.DUMP_BUDGETS.values()) + 1024 <= 64 * 10 ** 6
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """dump_outputs on stand-ins for the context, the matrix and the linear
+    system: file names, float64, the values as they stand on the device, the
+    per-rank suffix and the shared byte budget at N > 1."""
+    import types
+
+    import numpy as np
+
+    monkeypatch.setitem(bench.DUMP_BUDGETS, "csr_values", 8000)  # small budgets: the sampled path at a small size
+    monkeypatch.setitem(bench.DUMP_BUDGETS, "rhs", 1600)
+    vals = np.linspace(0.0, 1.0, 5000)
+    rhs = np.arange(100, dtype=np.float64)
+    ctx = types.SimpleNamespace(to_host=lambda dptr, count, dtype: vals[:count].astype(dtype))
+    bsr = types.SimpleNamespace(view=lambda: types.SimpleNamespace(values=1, nnz_blocks=vals.size, block_size=1))
+    ls = types.SimpleNamespace(rhs_host=lambda: rhs)
+    d = tmp_path / "one"
+    bench.dump_outputs(ctx, bsr, ls, str(d))
+    assert sorted(os.listdir(d)) == ["csr_values.npy", "rhs.npy"]
+    v = np.load(d / "csr_values.npy")
+    assert v.dtype == np.float64 and v.nbytes == bench.DUMP_BUDGETS["csr_values"]
+    assert np.array_equal(v, bench.dump_sample(vals, bench.DUMP_BUDGETS["csr_values"]))
+    assert np.array_equal(np.load(d / "rhs.npy"), rhs)
+    d = tmp_path / "four"
+    bench.dump_outputs(ctx, bsr, ls, str(d), rank=3, world=4)
+    assert sorted(os.listdir(d)) == ["csr_values_rank3.npy", "rhs_rank3.npy"]
+    assert np.load(d / "csr_values_rank3.npy").nbytes == bench.DUMP_BUDGETS["csr_values"] // 4

@@ -15,16 +15,16 @@ PASSES=${PASSES:-"trace fetch write"}
 mkdir -p $OUT
 for LEG in "$@"; do
   case $LEG in
-    c2) B="bench.py --no-extras --no-cpu-baseline --cg-iters 20"; K="k_assemble_cubes" ;;
-    c4) B="bench.py --no-headline --legs c4"; K="k_assemble_cubes" ;;
-    c2_spmv) B="bench.py --no-extras --no-cpu-baseline --cg-iters 20"; K="k_spmv_pat" ;;
-    c4_spmv) B="bench.py --no-headline --legs c4"; K="k_spmv_pat" ;;
-    c3) B="bench.py --no-headline --legs c3"; K="k_assemble_elast" ;;
-    c2_generic) B="bench.py --no-headline --legs c2_generic"; K="k_assemble_units" ;;
-    c2_arrays) B="bench.py --no-headline --legs c2_arrays"; K="k_assemble_cubes|k_cube_unstage" ;;
-    c2_arrays_natural) B="bench.py --no-headline --legs c2_arrays_natural"; K="k_assemble_cubes" ;;
-    unstructured) B="bench.py --no-headline --legs unstructured"; K="k_assemble_strip" ;;
-    generic_unstructured) B="bench.py --no-headline --legs generic_unstructured"; K="k_assemble_units" ;;
+    c2) B="bench.py --full --no-extras --no-cpu-baseline --cg-iters 20"; K="k_assemble_cubes" ;;
+    c4) B="bench.py --full --no-headline --legs c4"; K="k_assemble_cubes" ;;
+    c2_spmv) B="bench.py --full --no-extras --no-cpu-baseline --cg-iters 20"; K="k_spmv_pat" ;;
+    c4_spmv) B="bench.py --full --no-headline --legs c4"; K="k_spmv_pat" ;;
+    c3) B="bench.py --full --no-headline --legs c3"; K="k_assemble_elast" ;;
+    c2_generic) B="bench.py --full --no-headline --legs c2_generic"; K="k_assemble_units" ;;
+    c2_arrays) B="bench.py --full --no-headline --legs c2_arrays"; K="k_assemble_cubes|k_cube_unstage" ;;
+    c2_arrays_natural) B="bench.py --full --no-headline --legs c2_arrays_natural"; K="k_assemble_cubes" ;;
+    unstructured) B="bench.py --full --no-headline --legs unstructured"; K="k_assemble_strip" ;;
+    generic_unstructured) B="bench.py --full --no-headline --legs generic_unstructured"; K="k_assemble_units" ;;
     *) echo "unknown leg $LEG"; exit 2 ;;
   esac
   D=$OUT/$LEG
