@@ -174,9 +174,11 @@ __device__ __forceinline__ void put(double* p, double v)
     *p = v;
 }
 
-// HAS_RHS / RHS_ADD at compile time: the flush's global stores are then a
-// fixed, branch-free sequence, so the waits for the next layer's coordinates
-// count past them (vmcnt(N)) instead of draining them (vmcnt(0))
+// HAS_RHS / RHS_ADD at compile time: each flush's global stores are then a
+// fixed, branch-free sequence.  That alone does not keep them in flight: the
+// wait for the next layer's coordinates counts past them (vmcnt(N)) only if
+// the loop body holds one flush and no branch around it (the z walk at the
+// end of the kernel; tools/loop_waits.py shows the compiled loops)
 // amdgpu_waves_per_eu(3): 168 VGPRs, with the 49-row planes' 15.6 KB of LDS
 // 10 waves per CU (the 64-row planes' 19.3 KB keep 8 whatever the registers)
 // CANON: a lattice mesh in the caller's numbering (sparsity.hip canonical_lattice,
@@ -260,36 +262,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   // of draining everything (vmcnt(0)) at a branch join
   double pre[2][3];
   int32_t pid[2] = { 0, 0 };  // CANON: the caller's ids of the next staged layer's nodes
-  auto layer_ids = [&](int k, int64_t(&id)[2]) {
-    const int kk = is_local(g, k) ? k : g.k0;
+  // a node's id = its layer's first id (wave-uniform: kept in scalar registers,
+  // readfirstlane, so the address arithmetic of every layer's loads is a scalar
+  // base plus a per-lane constant) + its place in the layer (computed once)
+  auto layer_base = [&](int k) { return (int64_t)__builtin_amdgcn_readfirstlane(local_layer(g, k)) * g.L; };
+  int64_t xy_id[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int q = min(lane + 64 * h, kCol * kCol - 1);
-      int nx, ny;
-      node_xy(q, nx, ny);
-      nx = min(max(nx, 0), g.npx - 1);
-      ny = min(max(ny, 0), g.npy - 1);
-      id[h] = (int64_t)local_layer(g, kk) * g.L + nx + (int64_t)g.npx * ny;
-    }
-  };
+  for (int h = 0; h < 2; ++h) {
+    const int q = min(lane + 64 * h, kCol * kCol - 1);
+    int nx, ny;
+    node_xy(q, nx, ny);
+    nx = min(max(nx, 0), g.npx - 1);
+    ny = min(max(ny, 0), g.npy - 1);
+    xy_id[h] = nx + (int64_t)g.npx * ny;
+  }
+  auto clamp_layer = [&](int k) { return is_local(g, k) ? k : g.k0; };
   // CANON: the ids first (prefetch_ids, one step ahead), the coordinates through them
   auto prefetch_ids = [&](int k) {
     if constexpr (CANON) {
-      int64_t id[2];
-      layer_ids(k, id);
+      const int32_t* const lp = cc.phys + layer_base(clamp_layer(k));
 #pragma unroll
-      for (int h = 0; h < 2; ++h) pid[h] = cc.phys[id[h]];
+      for (int h = 0; h < 2; ++h) pid[h] = lp[xy_id[h]];
     }
   };
   auto load_layer = [&](int k) {
-    int64_t id[2];
-    layer_ids(k, id);
+    const double* const lc = CANON ? coords : coords + 3 * layer_base(clamp_layer(k));
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int64_t n = CANON ? (int64_t)pid[h] : id[h];
-      pre[h][0] = coords[3 * n];
-      pre[h][1] = coords[3 * n + 1];
-      pre[h][2] = coords[3 * n + 2];
+      const int64_t n = CANON ? (int64_t)pid[h] : xy_id[h];
+      pre[h][0] = lc[3 * n];
+      pre[h][1] = lc[3 * n + 1];
+      pre[h][2] = lc[3 * n + 2];
     }
   };
   auto store_layer = [&](int buf) {
@@ -314,9 +317,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   int64_t pf_rb = 0, pf_re = 0, pf_r = 0;
   uint64_t pf_slot = 0;
   double pf_rhs = 0.0;
+  const int64_t row_xy = min(nx, g.npx - 1) + (int64_t)g.npx * min(ny, g.npy - 1);  // the lane's row within its layer
   auto prefetch_rows = [&](int z) {  // clamped like load_layer: no branch
     const int zz = (z >= z0 && z < z1) ? z : z0;
-    const int64_t li = (int64_t)local_layer(g, zz) * g.L + min(nx, g.npx - 1) + (int64_t)g.npx * min(ny, g.npy - 1);
+    const int64_t lb = layer_base(zz);
+    const int64_t li = lb + row_xy;
     if constexpr (STAGE) {
       (void)li;  // the rows' maps are k_cube_unstage's
     }
@@ -327,8 +332,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     }
     else {
       pf_r = li;
-      pf_rb = rows[pf_r];
-      pf_re = rows[pf_r + 1];
+      pf_rb = (rows + lb)[row_xy];
+      pf_re = (rows + lb)[row_xy + 1];
       if constexpr (RHS_ADD) pf_rhs = rhs[pf_r];
     }
   };
@@ -339,9 +344,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   // and each x-run is 105 consecutive image values -- no masks, no
   // compaction, constant LDS offsets (flush_full)
   const bool xy_full = cx0 >= 1 && cx0 + kRun <= g.npx - 1 && cy0 >= 1 && cy0 + kRun <= g.npy - 1;
-  auto layer_full = [&](int z) {
-    return xy_full && z >= 1 && z + 1 <= g.nzc && local_layer(g, z - 1) < local_layer(g, z) &&
-           local_layer(g, z) < local_layer(g, z + 1);
+  // Such layers of a unit are one contiguous range [zf0, zf1) (wave-uniform,
+  // computed once): an owned layer z has local index z - k0, below every later
+  // owned layer's and below both ghost layers', so layers z and z + 1 are
+  // always in id order, and z - 1 and z are unless z = k0 (the ghost layer
+  // below, or no layer at all, under it).  With z + 1 <= nzc that leaves
+  // k0 + 1 <= z <= nzc - 1.  The z walk runs the range in a loop of its own
+  // whose body holds flush_full and no branch.
+  auto full_range = [&](int zlo, int zhi, int& zf0, int& zf1) {  // of the node layers [zlo, zhi)
+    const bool on = !CANON && xy_full && full_flush_on;
+    zf0 = on ? min(max(zlo, g.k0 + 1), zhi) : zhi;
+    zf1 = on ? max(min(zhi, g.nzc), zf0) : zhi;
   };
   auto flush_full = [&](int z) {
     const int b = z & 1;
@@ -382,6 +395,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     // stores 103, 104 -- value 103 twice with the same data -- and the lanes
     // past it repeat lane 52's): 7 stores per layer instead of 14
     const int t2 = min(2 * lane, 15 * kRun - 2);
+    // the 7 runs' image reads all issued before the first store (28 registers,
+    // free here: the cube's sums are dead): one LDS round trip before the
+    // stores instead of one per run
+    double ra[kRun][2];
+    if constexpr ((DIAG & 1) == 0 && (DIAG & 64) != 0) {
+#pragma unroll
+      for (int q = 0; q < kRun; ++q) {
+        ra[q][0] = img[15 * kRun * q + t2];
+        ra[q][1] = img[15 * kRun * q + t2 + 1];
+      }
+    }
 #pragma unroll
     for (int q = 0; q < kRun; ++q) {
       const int64_t dst = lane_i64(rb, kRun * q);
@@ -389,7 +413,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
         (void)dst;  // diagnostic: no value stores
       }
       else if constexpr ((DIAG & 64) != 0) {
-        const double a0 = img[15 * kRun * q + t2], a1 = img[15 * kRun * q + t2 + 1];
+        const double a0 = ra[q][0], a1 = ra[q][1];
         typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
         if constexpr ((DIAG & 32) != 0)
           __builtin_nontemporal_store(d2u{ a0, a1 }, reinterpret_cast<d2u*>(&vals[dst + t2]));
@@ -455,13 +479,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     typedef double d2u __attribute__((ext_vector_type(2), aligned(16)));
     const int64_t lz = (int64_t)local_layer(g, z) * g.L + cx0;
     const bool xok = lane < 2 * 8 * kRun / 2 && cx0 + (lane >> 3) < g.npx;  // pair `lane` is line lane / 8's
+    // a run past the box repeats run 0's store (always in the box), lanes
+    // without a line lane 0's pair: same address, same values -- 7 stores
+    // whatever the unit, so the waits after them count past them.  The image
+    // reads of all runs first (as in flush_full).
+    const int t = xok ? 2 * lane : 0;
+    d2u w[kRun];
 #pragma unroll
     for (int q = 0; q < kRun; ++q) {
-      if (cy0 + q >= g.npy) break;  // uniform
-      // lanes without a line repeat lane 0's pair (same address, same values)
-      const int t = xok ? 2 * lane : 0;
-      const d2u w = d2u{ img[2 * 8 * kRun * q + t], img[2 * 8 * kRun * q + t + 1] };
-      __builtin_nontemporal_store(w, reinterpret_cast<d2u*>(&cc.stage[16 * (lz + (int64_t)g.npx * (cy0 + q)) + t]));
+      const int qs = cy0 + q < g.npy ? q : 0;  // uniform
+      w[q] = d2u{ img[2 * 8 * kRun * qs + t], img[2 * 8 * kRun * qs + t + 1] };
+    }
+#pragma unroll
+    for (int q = 0; q < kRun; ++q) {
+      const int qs = cy0 + q < g.npy ? q : 0;
+      __builtin_nontemporal_store(w[q], reinterpret_cast<d2u*>(&cc.stage[16 * (lz + (int64_t)g.npx * (cy0 + qs)) + t]));
     }
     wave_lds_order();
     double2* const img2 = reinterpret_cast<double2*>(img);
@@ -470,16 +502,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
       img2[min(64 * i + lane, kAcc * STRIDE / 2 - 1)] = make_double2(0.0, 0.0);
     wave_lds_order();
   };
+  // the flush of any other layer (the z walk below picks flush_full for the
+  // complete ones): no branch on the layer here, so its 1 + 14 stores (1 + 7
+  // canonical, 7 staged) are a fixed sequence after the loop's loads
   auto flush = [&](int z) {
     if constexpr (STAGE) {
       flush_stage(z);
       return;
-    }
-    if constexpr (!CANON) {
-      if (full_flush_on && layer_full(z)) {
-        if constexpr (!(DIAG & 8)) flush_full(z);
-        return;
-      }
     }
     const int b = z & 1;
     const bool valid = lane < kRows && nx < g.npx && ny < g.npy;
@@ -857,14 +886,36 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   // the node layers of cube layer zc sit in buffers zc & 1 and (zc + 1) & 1;
   // layer zc + 2's coordinates are loaded at the top of iteration zc and
   // staged at its end (into buffer zc & 1, read for the last time by the
-  // cubes): their wait then counts past the flush's stores (vmcnt(N)), and no
-  // wait sits at the loop head, where the entry and the back edge would merge
-  // into the stricter one
+  // cubes).  Loads and stores share vmcnt and retire in order, and the loads
+  // are older than the flush's stores: the staging wait at the loop tail
+  // leaves the layer's stores in flight only when the compiler can count them,
+  // that is when every path from the loads to the tail issues the same
+  // stores.  So each loop below has ONE flush and no branch around it (a
+  // choice of flush inside the body made the tail wait vmcnt(0), draining the
+  // stores before the next layer's arithmetic could start); tools/loop_waits.py
+  // prints the loops' loads, stores and waits from the compiled code.
+  // CANON: the coordinates go through the caller's ids, themselves loaded one
+  // step before (next_layer: layer k's coordinates from the ids in pid, then
+  // layer k + 1's ids into pid), so no trip waits for ids it has just asked for
+  auto next_layer = [&](int k) {
+    load_layer(k);
+    prefetch_ids(k + 1);
+  };
+  // before a loop is entered the ids on their way are waited for (an empty
+  // statement that reads them): a loop's first instruction is reached from its
+  // entry and from its back edge, and a wait there takes the stricter of the
+  // two counts -- with the ids just asked for on entry that is vmcnt(1),
+  // which on the back edge drains the layer's stores.  The wait sits behind the
+  // staging of coordinates loaded before those ids, so it costs no latency.
+  auto settle_ids = [&]() {
+    if constexpr (CANON) asm volatile("" : "+v"(pid[0]), "+v"(pid[1]));
+  };
   prefetch_ids(zc_first);
   load_layer(zc_first);
   store_layer(zc_first & 1);
   prefetch_ids(zc_first + 1);
   load_layer(zc_first + 1);
+  prefetch_ids(zc_first + 2);
   if constexpr (NCZ == 1) {  // the bottom layer into the corner registers before the top overwrites it
     wave_lds_order();
     prime_corners(zc_first);
@@ -873,10 +924,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   store_layer((zc_first + 1) & 1);
   wave_lds_order();
   if constexpr (CARRY && NCZ == 2) prime_corners(zc_first);
+  settle_ids();
   int zc = zc_first;
   if (zc < z0) {  // the cube layer below the segment: its top corners only, no flush
-    prefetch_ids(zc + 2);
-    load_layer(zc + 2);
+    next_layer(zc + 2);
     wave_lds_order();
     cubes(zc);
     wave_lds_order();
@@ -888,23 +939,43 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
       wave_lds_order();
     }
     store_layer(zc & 1);
+    settle_ids();
     ++zc;
   }
-  // every layer of the loop completes a node layer of the segment (z0 <= zc
-  // <= zc_last < z1): the flush is unconditional, so the offsets' prefetch
-  // stays ahead of the cubes
-  for (; zc <= zc_last; ++zc) {
-    // the offsets of the rows this iteration completes, then the coordinates
-    // of layer zc + 2: the flush waits for the offsets only (counted vmcnt)
-    prefetch_ids(zc + 2);  // CANON: the next staged layer's caller ids, in flight during the cubes
+  // every layer from here completes a node layer of the segment (z0 <= zc <=
+  // zc_last < z1).  One trip: the offsets of the rows it completes, then the
+  // coordinates of layer zc + 2 (V bit 16: before the cubes, their latency
+  // hides behind them; else after, their 12 registers not live across them),
+  // the cubes, the flush, the staging.
+  auto layer_step = [&](int zc, auto&& fl) {
     prefetch_rows(zc);
-    if constexpr ((DIAG & 16) != 0) load_layer(zc + 2);  // before the cubes: their latency hides behind them
+    if constexpr ((DIAG & 16) != 0) next_layer(zc + 2);
     wave_lds_order();
     cubes(zc);
-    if constexpr ((DIAG & 16) == 0) load_layer(zc + 2);  // after the cubes: its 12 registers are not live across them
+    if constexpr ((DIAG & 16) == 0) next_layer(zc + 2);
     wave_lds_order();
-    flush(zc);
+    fl(zc);
     store_layer(zc & 1);
+  };
+  // the layers below the complete range, the range, the layers above it: the
+  // general loop is compiled once and entered twice (ph), the complete-layer
+  // loop between its two passes
+  int zf0, zf1;
+  full_range(zc, zc_last + 1, zf0, zf1);
+#pragma nounroll
+  for (int ph = 0; ph < 2; ++ph) {
+    const int zend = ph == 0 ? zf0 : zc_last + 1;
+#pragma nounroll
+    for (; zc < zend; ++zc) layer_step(zc, flush);
+    if constexpr (!CANON) {
+      if (ph == 0) {
+#pragma nounroll
+        for (; zc < zf1; ++zc)
+          layer_step(zc, [&](int z) {
+            if constexpr (!(DIAG & 8)) flush_full(z);
+          });
+      }
+    }
   }
   if (zc_last + 1 >= z0 && zc_last + 1 < z1) {  // the box's top layer (no cube above)
     prefetch_rows(zc_last + 1);
