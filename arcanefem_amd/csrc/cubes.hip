@@ -29,6 +29,17 @@
 // by each row's present neighbours into a flat LDS image, then each x-run of
 // 7 rows (contiguous in the matrix) with consecutive lanes.
 //
+// Single writer (the default instances: z carry, x and y exchange, dummy
+// rows; V bit 2048): after the carry and the two exchanges a cube keeps 7 of
+// its 19 edges and corner 3's |det| sum, each already the full sum over the
+// cubes that share it, and each (row, offset) slot of a node layer takes
+// exactly one of them per layer cycle.  So the 15 adds are plain LDS stores,
+// nothing is zero-filled, the buffers are row-major ([64 rows][15 offsets]:
+// the unit's 49 rows are the flat image already) and a complete layer's flush
+// writes back the 49 diagonals only.  The instances without an exchange, with
+// 49-row planes or without the dummy rows keep the adds into zeroed
+// [15][STRIDE] planes described above.  Same bits either way.
+//
 // Applies to meshes from afem_mesh_create_structured (3D, NB_DOF 1, any
 // z-slab: the columns follow the local numbering -- owned layers, then the
 // ghost layer below, then above -- so the sorted column order of a row next to
@@ -42,6 +53,7 @@
 #include "afem_internal.hpp"
 
 #include <algorithm>
+#include <limits>
 
 // the 64-row instances cannot reach the 3-waves register target (their LDS
 // allows 2 per SIMD): the compiler says so for each; expected
@@ -80,6 +92,9 @@ struct CubeGeom {
   double s_coef;     // coef / 6
   double f_meas;     // f / 24
   int full_flush;    // flush_full for layers whose rows are all complete (AFEM_CUBES_FULL=0: not)
+  double acc_init;   // single-writer instances (V bit 2048): the accumulators' first fill (0.0;
+                     // AFEM_CUBES_ACC_INIT=nan: a quiet NaN, to show that no flush reads a slot
+                     // its layer did not write); the adding instances fill with 0.0 whatever this is
 };
 
 // is global node layer k one of the slab's local layers (owned or ghost)?
@@ -204,7 +219,12 @@ struct CubeCanon {
 // row stores in the canonical flush, 1024 the canonical path STAGED (its rows
 // written in lattice order as one 128-B line each -- the 15 values by Kuhn
 // offset, the |det| sum at 15 -- and moved into the caller's rows by
-// k_cube_unstage, caller row by caller row: whole-line stores).  Diagnostic
+// k_cube_unstage, caller row by caller row: whole-line stores), 2048 single
+// writer (SW in the kernel: with the carry, both exchanges and the dummy rows
+// every accumulator slot takes one sum per layer cycle, so the sums are stored
+// into a buffer laid out as the image, flush_full writes back the diagonal
+// alone and nothing is zero-filled; without 2048 the sums are added into
+// zeroed offset planes, the same bits).  Diagnostic
 // ablations (values wrong): 1 no value stores in the complete-layer flush, 2
 // one LDS add per cube (the sum of its sums) instead of its 15, 4 no cube
 // arithmetic, 8 no complete-layer flush.  Measured (r05d/e, C2 / C4, one
@@ -214,7 +234,7 @@ struct CubeCanon {
 // of 16 | 32 | 64: C2 0.4632 -> 0.4608 ms, C4 4.194 -> 4.097 ms (r05i); 512:
 // random-numbered arrays (canonical path) 1.581 -> 1.538 ms (r05k); 1024 there:
 // 1.539 -> 1.103 ms (r05as: 0.587 ms cube pass + 0.532 ms k_cube_unstage).
-constexpr int kCubesV = 16 | 32 | 64 | 256 | 512 | 1024;
+constexpr int kCubesV = 16 | 32 | 64 | 256 | 512 | 1024 | 2048;
 
 // register budget: 64-row planes + one coordinate layer = 17.3 KB of LDS, 9
 // waves per CU, so 2 per SIMD whatever the registers (256 VGPRs, no spill);
@@ -226,7 +246,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     CubeGeom g, const int64_t* __restrict__ rows, const double* __restrict__ coords, double* __restrict__ vals,
     double* __restrict__ rhs, CubeCanon cc)
 {
-  __shared__ __align__(16) double acc[2][kAcc][STRIDE];  // STRIDE >= 49 rows per offset plane
+  // STRIDE >= 49 rows per offset plane; the single-writer instances (SW below)
+  // use each buffer's 15 x 64 doubles row-major instead, slot o of row r at 15 r + o
+  __shared__ __align__(16) double acc[2][kAcc][STRIDE];
   // SoA coordinates of the node layers being read: with the carry the bottom
   // corners come from registers (Xc), so one layer -- the cube layer's top --
   // is read, and the next one is staged over it after the cubes
@@ -305,7 +327,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
       cz[buf][2][q] = pre[h][2];
     }
   };
-  for (int i = lane; i < 2 * kAcc * STRIDE; i += 64) (&acc[0][0][0])[i] = 0.0;
+  // DROWS (V bit 256, 64-row planes): dummy rows for the corners outside the
+  // unit (slot_d below).  SW (V bit 2048, with the carry, both exchanges and
+  // the dummy rows): SINGLE WRITER.  Every slot (row, offset) of a node layer
+  // then takes exactly one sum per layer cycle -- after the carry and the
+  // exchanges a cube keeps the 7 edges 0-3, 0-7, 1-7, 2-7, 3-7, 1-3, 2-3 and
+  // corner 3's |det| sum, each geometric edge is exactly one cube's kept edge,
+  // and that cube's lane is in the wave for every row of the unit -- so the
+  // sums are STORED, not added: no zero fill anywhere, and the buffer is laid
+  // out as the image (slot o of row r at 15 r + o, the dummy rows 49..63
+  // behind: 960 doubles as before), so flush_full writes back the diagonal
+  // alone.  Node layer z's slots 0..3 come from cube layer z - 1, 4..14 from
+  // cube layer z; a slot of an absent neighbour (and a dummy row) holds stale
+  // data, read only behind the presence mask.  Bitwise the adding instances:
+  // 0.0 + x = x, and no summation order changes.
+  constexpr bool DROWS = (DIAG & 256) != 0 && STRIDE == 64;
+  constexpr bool SW = DROWS && CARRY && XEX && YEX && (DIAG & 2048) != 0 && (DIAG & 2) == 0;
+  // slot o of row r of buffer b
+  auto slot = [&](int b, int r, int o) -> double* {
+    return SW ? &acc[b][0][0] + kAcc * r + o : &acc[b][o][r];
+  };
+  {
+    const double fill = SW ? g.acc_init : 0.0;
+    for (int i = lane; i < 2 * kAcc * STRIDE; i += 64) (&acc[0][0][0])[i] = fill;
+  }
 
   // ---- node layer z complete: write its 49 rows (values compacted by the present neighbours) + RHS.
   // The rows' offsets are loaded before the layer's cubes (prefetch_rows), so
@@ -363,7 +408,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     double sum = 0.0;
 #pragma unroll
     for (int o = 0; o < 15; ++o) {
-      v[o] = acc[b][o][lr];
+      v[o] = *slot(b, lr, o);
       if (o != 7) sum += v[o];
     }
     const double meas = v[7];
@@ -379,13 +424,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     double* img = &acc[b][0][0];
     // (each lane storing its own row from registers instead -- 7 16-B stores at a
     // 120-B lane stride -- measured 3.19 against 0.456 ms, r05aw: the image stays)
-    wave_lds_order();  // every lane's accumulator reads before the image overwrites them
-    // row L at [15 L, 15 L + 15): lanes past the 49 rows write into
-    // [735, 960) of the buffer, which no store reads (64-row planes), or --
-    // 49-row planes, whose buffer ends at 735 -- repeat row 48's writes with
-    // row 48's values (they read row 48: same addresses, same values)
+    if constexpr (SW) {
+      // the buffer is the image already: the diagonal goes where the |det| sum
+      // was (the lane's own row: no other lane reads that slot before this
+      // store), one LDS store instead of 15; the lanes past the 49 rows do the
+      // same to their dummy rows
+      img[kAcc * lane + 7] = v[7];
+    }
+    else {
+      wave_lds_order();  // every lane's accumulator reads before the image overwrites them
+      // row L at [15 L, 15 L + 15): lanes past the 49 rows write into
+      // [735, 960) of the buffer, which no store reads (64-row planes), or --
+      // 49-row planes, whose buffer ends at 735 -- repeat row 48's writes with
+      // row 48's values (they read row 48: same addresses, same values)
 #pragma unroll
-    for (int o = 0; o < 15; ++o) img[15 * (STRIDE == 64 ? lane : lr) + o] = v[o];
+      for (int o = 0; o < 15; ++o) img[15 * (STRIDE == 64 ? lane : lr) + o] = v[o];
+    }
     wave_lds_order();
     // x-run q = rows 7q .. 7q + 6: 105 values contiguous in vals from row 7q's
     // first one; the second store's lanes past 105 repeat value 104 (same
@@ -430,21 +484,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
       }
     }
     wave_lds_order();
-    if constexpr ((kAcc * STRIDE) % 2 == 0) {
+    if constexpr (SW) {
+      // no zero fill: the next cycle's stores overwrite every slot that is read
+    }
+    else if constexpr ((kAcc * STRIDE) % 2 == 0) {
       double2* const img2 = reinterpret_cast<double2*>(img);
 #pragma unroll
       for (int i = 0; i < (kAcc * STRIDE / 2 + 63) / 64; ++i)
         img2[min(64 * i + lane, kAcc * STRIDE / 2 - 1)] = make_double2(0.0, 0.0);
+      wave_lds_order();
     }
     else {
 #pragma unroll
       for (int i = 0; i < (kAcc * STRIDE + 63) / 64; ++i) img[min(64 * i + lane, kAcc * STRIDE - 1)] = 0.0;
+      wave_lds_order();
     }
-    wave_lds_order();
   };
   // STAGE: node layer z's rows into their lattice-order lines, line L = the
   // row's 15 values by Kuhn offset o and its |det| sum at 15 (an absent
-  // neighbour's value is the zero its slot holds and is never moved); x-run q
+  // neighbour's value is 0.0 -- the zero its slot holds, or selected here when
+  // the slots are stored to (SW) -- and is never moved); x-run q
   // = 7 lines = 112 consecutive doubles, one 16-B non-temporal store per lane
   auto flush_stage = [&](int z) {
     const int b = z & 1;
@@ -463,7 +522,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     const int lr = min(lane, STRIDE - 1);
 #pragma unroll
     for (int o = 0; o < 15; ++o) {
-      v[o] = acc[b][o][lr];
+      v[o] = *slot(b, lr, o);
       if (o != 7 && ((mask >> o) & 1u)) sum += v[o];
     }
     const double meas = v[7];
@@ -471,8 +530,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     wave_lds_order();  // every lane's accumulator reads before the image overwrites them
     double* img = &acc[b][0][0];
     if (lane < kRows) {  // 49 lines of 16 = 784 of the buffer's 960 doubles
+      // SW: an absent neighbour's slot holds stale data, the line takes 0.0 for it
 #pragma unroll
-      for (int o = 0; o < 15; ++o) img[16 * lane + o] = v[o];
+      for (int o = 0; o < 15; ++o) img[16 * lane + o] = (!SW || o == 7 || ((mask >> o) & 1u)) ? v[o] : 0.0;
       img[16 * lane + 15] = meas;
     }
     wave_lds_order();
@@ -496,11 +556,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
       __builtin_nontemporal_store(w[q], reinterpret_cast<d2u*>(&cc.stage[16 * (lz + (int64_t)g.npx * (cy0 + qs)) + t]));
     }
     wave_lds_order();
-    double2* const img2 = reinterpret_cast<double2*>(img);
+    if constexpr (!SW) {
+      double2* const img2 = reinterpret_cast<double2*>(img);
 #pragma unroll
-    for (int i = 0; i < (kAcc * STRIDE / 2 + 63) / 64; ++i)
-      img2[min(64 * i + lane, kAcc * STRIDE / 2 - 1)] = make_double2(0.0, 0.0);
-    wave_lds_order();
+      for (int i = 0; i < (kAcc * STRIDE / 2 + 63) / 64; ++i)
+        img2[min(64 * i + lane, kAcc * STRIDE / 2 - 1)] = make_double2(0.0, 0.0);
+      wave_lds_order();
+    }
   };
   // the flush of any other layer (the z walk below picks flush_full for the
   // complete ones): no branch on the layer here, so its 1 + 14 stores (1 + 7
@@ -533,7 +595,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     const int lr = min(lane, STRIDE - 1);  // lanes past the 49 rows read a row they do not use
 #pragma unroll
     for (int o = 0; o < 15; ++o) {
-      v[o] = acc[b][o][lr];
+      v[o] = *slot(b, lr, o);
       if (o != 7 && ((mask >> o) & 1u)) sum += v[o];
     }
     const double meas = v[7];
@@ -645,17 +707,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     }
     }
     wave_lds_order();
-    if constexpr ((kAcc * STRIDE) % 2 == 0) {  // 16-B stores (64-row planes: buffers 16-B aligned)
+    if constexpr (SW) {
+      // no zero fill (the image stays as stale data behind the next cycle's masks)
+    }
+    else if constexpr ((kAcc * STRIDE) % 2 == 0) {  // 16-B stores (64-row planes: buffers 16-B aligned)
       double2* const img2 = reinterpret_cast<double2*>(img);
 #pragma unroll
       for (int i = 0; i < (kAcc * STRIDE / 2 + 63) / 64; ++i)
         img2[min(64 * i + lane, kAcc * STRIDE / 2 - 1)] = make_double2(0.0, 0.0);
+      wave_lds_order();
     }
     else {
 #pragma unroll
       for (int i = 0; i < (kAcc * STRIDE + 63) / 64; ++i) img[min(64 * i + lane, kAcc * STRIDE - 1)] = 0.0;
+      wave_lds_order();
     }
-    wave_lds_order();
   };
 
   // ---- cube layer zc: the lane's cube, its 6 tets, 19 edge sums and 8 corner |det| sums
@@ -701,15 +767,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   // not this unit's) get real sums too, so that buffer is zeroed after the
   // layer below (its next use is node layer z0 + 1).  Rows inside the unit but
   // outside the box take their sums in their own slots and are never stored.
-  constexpr bool DROWS = (DIAG & 256) != 0 && STRIDE == 64;
-  int row4[4];
+  // SW: the same rows, the sums stored (a dummy row's slot then takes the
+  // stores of several corners: nothing reads it), and no buffer is cleared.
+  int row4[4];  // the corner's row (SW: its first slot, 15 x row)
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int rx = ci - 1 + (k & 1), ry = cj - 1 + (k >> 1);
     const bool inx = rx >= 0 && rx < kRun, iny = ry >= 0 && ry < kRun;
-    row4[k] = (inx && iny) ? rx + kRun * ry : (!inx ? kRows + cj : kRows + 8 + rx);
+    row4[k] = (SW ? kAcc : 1) * ((inx && iny) ? rx + kRun * ry : (!inx ? kRows + cj : kRows + 8 + rx));
   }
-  auto base_d = [&](int bb, int bt, int c) { return &acc[cbit(c, 2) ? bt : bb][0][0] + row4[c & 3]; };
+  // corner c's slot o
+  auto slot_d = [&](int bb, int bt, int c, int o) {
+    return &acc[cbit(c, 2) ? bt : bb][0][0] + row4[c & 3] + (SW ? 1 : STRIDE) * o;
+  };
+  // a corner's sum into its slot: stored (SW) or added
+  auto sum_d = [&](double* p, double x) {
+    if constexpr (SW)
+      *p = x;
+    else
+      atomicAdd(p, x);
+  };
   // the top face's carried sums into LDS (the box's top node layer: no cube above)
   auto add_top = [&](int zc) {
     uint32_t inm;
@@ -717,11 +794,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     corner_frame(zc, inm, bb, bt);
     auto kept = [&](int c, double x) { return ((inm >> c) & 1u) ? x : 0.0; };
     constexpr int ta[5] = { 4, 4, 4, 5, 6 }, tb[5] = { 5, 6, 7, 7, 7 };
+    if constexpr (SW) {
+      // the carried top-face sums are not exchanged, so several lanes still ADD
+      // into one slot here: the dz = 0 slots (4..10) of the layer's rows are
+      // cleared first (they hold the flush's leavings of two layers ago), then
+      // the adds as in the adding instances -- the same bits.  Once per unit
+      // at the box's top.
+#pragma unroll
+      for (int o = 4; o <= 10; ++o) (&acc[bt][0][0])[kAcc * lane + o] = 0.0;
+      wave_lds_order();
+    }
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
       if constexpr (DROWS) {
-        atomicAdd(base_d(bb, bt, ta[i]) + STRIDE * edge_o(ta[i], tb[i]), ce[i]);
-        atomicAdd(base_d(bb, bt, tb[i]) + STRIDE * edge_o(tb[i], ta[i]), ce[i]);
+        atomicAdd(slot_d(bb, bt, ta[i], edge_o(ta[i], tb[i])), ce[i]);
+        atomicAdd(slot_d(bb, bt, tb[i], edge_o(tb[i], ta[i])), ce[i]);
       }
       else {
         atomicAdd(base_at(inm, bb, bt, ta[i]) + STRIDE * edge_o(ta[i], tb[i]), kept(ta[i], ce[i]));
@@ -731,7 +818,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
 #pragma unroll
     for (int c = 4; c < 8; ++c) {
       if constexpr (DROWS)
-        atomicAdd(base_d(bb, bt, c) + STRIDE * 7, cm[c - 4]);
+        atomicAdd(slot_d(bb, bt, c, 7), cm[c - 4]);
       else
         atomicAdd(base_at(inm, bb, bt, c) + STRIDE * 7, kept(c, cm[c - 4]));
     }
@@ -861,8 +948,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
             dsum += ev[a][b];
           }
           else if constexpr (DROWS) {
-            atomicAdd(base_d(bb_, bt_, a) + STRIDE * edge_o(a, b), ev[a][b]);
-            atomicAdd(base_d(bb_, bt_, b) + STRIDE * edge_o(b, a), ev[a][b]);
+            sum_d(slot_d(bb_, bt_, a, edge_o(a, b)), ev[a][b]);
+            sum_d(slot_d(bb_, bt_, b, edge_o(b, a)), ev[a][b]);
           }
           else {
             atomicAdd(base_at(inm, bb_, bt_, a) + STRIDE * edge_o(a, b), kept(a, ev[a][b]));
@@ -875,7 +962,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
         if constexpr (DIAG & 2)
           dsum += mv[c];
         else if constexpr (DROWS)
-          atomicAdd(base_d(bb_, bt_, c) + STRIDE * 7, mv[c]);  // |det| sums
+          sum_d(slot_d(bb_, bt_, c, 7), mv[c]);  // |det| sums
         else
           atomicAdd(base_at(inm, bb_, bt_, c) + STRIDE * 7, kept(c, mv[c]));  // |det| sums
       }
@@ -931,7 +1018,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     wave_lds_order();
     cubes(zc);
     wave_lds_order();
-    if constexpr (DROWS) {  // node layer z0 - 1's buffer took real sums: clear it for node layer z0 + 1
+    // node layer z0 - 1's buffer took real sums: clear it for node layer z0 + 1
+    // (SW: not needed, node layer z0 + 1's cycle stores to every slot it reads)
+    if constexpr (DROWS && !SW) {
       double2* const b2 = reinterpret_cast<double2*>(&acc[zc & 1][0][0]);
 #pragma unroll
       for (int i = 0; i < (kAcc * STRIDE / 2 + 63) / 64; ++i)
@@ -1154,6 +1243,10 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
   g.f_meas = f / 24.0;
   const char* fe = variant("AFEM_CUBES_FULL");
   g.full_flush = (fe && atoi(fe) == 0) ? 0 : 1;
+  // the single-writer instances' first accumulator fill (a test's knob: with a NaN
+  // there the outputs stay finite only if no flush reads a slot its layer did not write)
+  const char* ie = variant("AFEM_CUBES_ACC_INIT");
+  g.acc_init = (ie && (ie[0] == 'n' || ie[0] == 'N')) ? std::numeric_limits<double>::quiet_NaN() : 0.0;
   const int64_t n_units = (int64_t)g.tx * g.ty * g.ns;
   AFEM_REQUIRE(n_units < (int64_t(1) << 31), AFEM_ERR_LIMIT, "cube kernel: too many units");
   // accumulator planes of 64 rows (19.3 KB of LDS, 8 waves per CU), or of 49
@@ -1191,12 +1284,12 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
     switch (diag) {
 #define AFEM_CUBES_D(D)                                                                                              \
   case D:                                                                                                            \
-    kern = canon ? &k_assemble_cubes<64, true, true, true, true, true, false, D>                                    \
+    kern = canon ? &k_assemble_cubes<64, true, true, true, true, true, false, (D) & ~1024>                          \
                  : &k_assemble_cubes<64, true, true, true, false, true, false, D>;                                  \
     break;
       AFEM_CUBES_D(0) AFEM_CUBES_D(112) AFEM_CUBES_D(kCubesV | 1) AFEM_CUBES_D(kCubesV | 4)
       AFEM_CUBES_D(kCubesV | 8) AFEM_CUBES_D(kCubesV | 2) AFEM_CUBES_D(kCubesV & ~512) AFEM_CUBES_D(kCubesV & ~1024)
-      AFEM_CUBES_D(kCubesV & ~32)
+      AFEM_CUBES_D(kCubesV & ~32) AFEM_CUBES_D(kCubesV & ~2048) AFEM_CUBES_D(kCubesV & ~(1024 | 2048))
 #undef AFEM_CUBES_D
       default: break;
     }
@@ -1225,7 +1318,7 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
   case D:                                                                                                            \
     kern = &k_assemble_cubes<64, true, true, true, true, false, false, D>;                                          \
     break;
-        AFEM_CUBES_S(kCubesV | 1024 | 1) AFEM_CUBES_S(kCubesV | 1024 | 4)
+        AFEM_CUBES_S(kCubesV | 1024 | 1) AFEM_CUBES_S(kCubesV | 1024 | 4) AFEM_CUBES_S(kCubesV & ~2048)
 #undef AFEM_CUBES_S
         default: break;
       }
