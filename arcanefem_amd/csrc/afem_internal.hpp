@@ -295,6 +295,11 @@ struct Structure {
   bool cube_natural = false;
   int nat_axes[3] = { 0, 1, 2 };
   int64_t nat_L[3] = { 0, 0, 0 };
+  // generator boxes, slabs and natural lattices: the constant by which a row's
+  // first-value offset grows from one local layer to the next, over the layers
+  // a cube unit's complete range can hold (cubes.hip cube_row_stride, checked
+  // on the device when the structure is built); 0: none, or not one constant
+  int64_t cube_row_stride = 0;
   DevBuf<int32_t> cube_phys;
   DevBuf<int64_t> cube_rb;
   DevBuf<uint64_t> cube_slot;
@@ -509,6 +514,7 @@ bool lattice_coords(Ctx& ctx, const Mesh& m, int64_t n_rows, DevBuf<int32_t> lay
 void assemble_scalar(Bsr& b, double coef, double f, double* rhs, int rhs_add);
 // the cell-first cube kernel on generator boxes / slabs (cubes.hip); false: not applicable
 bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add);
+void cube_row_stride(const Mesh& m, Structure& s, int nb_dof);  // sets s.cube_row_stride (structure build)
 void assemble_elasticity_tri(Bsr& b, double lambda, double mu2);
 void assemble_elasticity_tet(Bsr& b, double lambda, double mu2, double c0, const double* f, double* rhs, int rhs_add);
 void apply_neumann(Mesh& m, int k, int mode, const double* v, int64_t n_faces, const int32_t* face_nodes,

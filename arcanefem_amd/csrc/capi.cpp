@@ -693,6 +693,7 @@ int afem_bsr_get_stats(afem_bsr* b, afem_bsr_stats* st)
   st->uniform_instance_slices = b->s.n_ur;
   st->general_slices = b->s.n_ms + b->s.n_mb;
   st->cube_axes = b->s.cube_natural ? b->s.nat_axes[0] + 3 * b->s.nat_axes[1] + 9 * b->s.nat_axes[2] : 0;
+  st->cube_row_stride = b->s.cube_row_stride;
   st->last_kernel = b->last_kernel;
   API_END
 }

@@ -92,9 +92,11 @@ struct CubeGeom {
   double s_coef;     // coef / 6
   double f_meas;     // f / 24
   int full_flush;    // flush_full for layers whose rows are all complete (AFEM_CUBES_FULL=0: not)
-  double acc_init;   // single-writer instances (V bit 2048): the accumulators' first fill (0.0;
-                     // AFEM_CUBES_ACC_INIT=nan: a quiet NaN, to show that no flush reads a slot
-                     // its layer did not write); the adding instances fill with 0.0 whatever this is
+  double acc_init;   // single-writer instances (V bit 2048): no first fill of the accumulators (0.0),
+                     // or, AFEM_CUBES_ACC_INIT=nan, a quiet NaN, to show that no flush reads a slot
+                     // its layer did not write; the adding instances fill with 0.0 whatever this is
+  int64_t row_stride;  // Structure::cube_row_stride: a row's offset on local layer l + 1 minus the one on
+                       // layer l, for every layer a complete range can hold (0: not one constant)
 };
 
 // is global node layer k one of the slab's local layers (owned or ghost)?
@@ -234,7 +236,12 @@ struct CubeCanon {
 // of 16 | 32 | 64: C2 0.4632 -> 0.4608 ms, C4 4.194 -> 4.097 ms (r05i); 512:
 // random-numbered arrays (canonical path) 1.581 -> 1.538 ms (r05k); 1024 there:
 // 1.539 -> 1.103 ms (r05as: 0.587 ms cube pass + 0.532 ms k_cube_unstage).
-constexpr int kCubesV = 16 | 32 | 64 | 256 | 512 | 1024 | 2048;
+// 4096 (box and natural-lattice instances; the canonical ones never carry it):
+// scalar row bases in the complete-layer loop -- where the structure's row
+// offsets advance by one constant per layer (CubeGeom::row_stride != 0) that
+// loop loads no row offsets (RS in the kernel); measured in DESIGN.md §3.1e (r09a).
+constexpr int kCubesBase = 16 | 32 | 64 | 256 | 512 | 1024 | 2048;  // the default up to r08a
+constexpr int kCubesV = kCubesBase | 4096;
 
 // register budget: 64-row planes + one coordinate layer = 17.3 KB of LDS, 9
 // waves per CU, so 2 per SIMD whatever the registers (256 VGPRs, no spill);
@@ -307,16 +314,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
       for (int h = 0; h < 2; ++h) pid[h] = lp[xy_id[h]];
     }
   };
-  auto load_layer = [&](int k) {
+  auto load_layer_to = [&](int k, double (&dst)[2][3]) {
     const double* const lc = CANON ? coords : coords + 3 * layer_base(clamp_layer(k));
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int64_t n = CANON ? (int64_t)pid[h] : xy_id[h];
-      pre[h][0] = lc[3 * n];
-      pre[h][1] = lc[3 * n + 1];
-      pre[h][2] = lc[3 * n + 2];
+      dst[h][0] = lc[3 * n];
+      dst[h][1] = lc[3 * n + 1];
+      dst[h][2] = lc[3 * n + 2];
     }
   };
+  auto load_layer = [&](int k) { load_layer_to(k, pre); };
   auto store_layer = [&](int buf) {
     buf = NCZ == 1 ? 0 : buf;
 #pragma unroll
@@ -347,7 +355,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   auto slot = [&](int b, int r, int o) -> double* {
     return SW ? &acc[b][0][0] + kAcc * r + o : &acc[b][o][r];
   };
-  {
+  // SW: no slot is read before its layer cycle stored to it, so there is no
+  // first fill either, unless the knob asks for the NaN that shows it
+  if (!SW || g.acc_init != g.acc_init) {
     const double fill = SW ? g.acc_init : 0.0;
     for (int i = lane; i < 2 * kAcc * STRIDE; i += 64) (&acc[0][0][0])[i] = fill;
   }
@@ -401,7 +411,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     zf0 = on ? min(max(zlo, g.k0 + 1), zhi) : zhi;
     zf1 = on ? max(min(zhi, g.nzc), zf0) : zhi;
   };
-  auto flush_full = [&](int z) {
+  // RS (V bit 4096, with g.row_stride != 0): the range's layers are consecutive
+  // local layers and a row's offset grows by one constant from each to the
+  // next (checked once per structure, cube_row_stride below), so its loop
+  // loads no offsets: the 7 x-runs' first values of the range's first layer
+  // are loaded once, with the unit's first coordinates, kept as 7 wave-uniform
+  // pointers into the values and advanced by the constant per layer.  The loop's only
+  // loads are then the coordinates of two layers ahead, and flush_full's first
+  // store waits for nothing the previous layer's stores are queued behind
+  // (loads and stores retire in order: the wait for offsets asked for after
+  // layer z - 1's stores drained those stores, a quarter of a layer later).
+  constexpr bool RS = !CANON && (DIAG & 4096) != 0;
+  int64_t rs_rb = 0;
+  auto load_run_bases = [&](int z) {  // clamped like prefetch_rows: no branch
+    const int zz = (z >= z0 && z < z1) ? z : z0;
+    rs_rb = (rows + layer_base(zz))[row_xy];
+  };
+  // (sb: where the 7 x-runs' first values go, wave-uniform, V bit 4096; null: by the lanes' prefetched offsets)
+  auto flush_full = [&](int z, double* const* sb) {
     const int b = z & 1;
     const int lr = min(lane, STRIDE - 1);  // lanes past the 49 rows read a row they do not use
     double v[15];
@@ -462,7 +489,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     }
 #pragma unroll
     for (int q = 0; q < kRun; ++q) {
-      const int64_t dst = lane_i64(rb, kRun * q);
+      double* const dst = sb ? sb[q] : vals + lane_i64(rb, kRun * q);
       if constexpr ((DIAG & 1) != 0) {
         (void)dst;  // diagnostic: no value stores
       }
@@ -470,17 +497,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
         const double a0 = ra[q][0], a1 = ra[q][1];
         typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
         if constexpr ((DIAG & 32) != 0)
-          __builtin_nontemporal_store(d2u{ a0, a1 }, reinterpret_cast<d2u*>(&vals[dst + t2]));
+          __builtin_nontemporal_store(d2u{ a0, a1 }, reinterpret_cast<d2u*>(&dst[t2]));
         else
-          *reinterpret_cast<d2u*>(&vals[dst + t2]) = d2u{ a0, a1 };
+          *reinterpret_cast<d2u*>(&dst[t2]) = d2u{ a0, a1 };
       }
       else if constexpr ((DIAG & 32) != 0) {
-        __builtin_nontemporal_store(img[15 * kRun * q + lane], &vals[dst + lane]);
-        __builtin_nontemporal_store(img[15 * kRun * q + t1], &vals[dst + t1]);
+        __builtin_nontemporal_store(img[15 * kRun * q + lane], &dst[lane]);
+        __builtin_nontemporal_store(img[15 * kRun * q + t1], &dst[t1]);
       }
       else {
-        vals[dst + lane] = img[15 * kRun * q + lane];
-        vals[dst + t1] = img[15 * kRun * q + t1];
+        dst[lane] = img[15 * kRun * q + lane];
+        dst[t1] = img[15 * kRun * q + t1];
       }
     }
     wave_lds_order();
@@ -997,12 +1024,32 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   auto settle_ids = [&]() {
     if constexpr (CANON) asm volatile("" : "+v"(pid[0]), "+v"(pid[1]));
   };
+  // the complete range of the unit's node layers (the walk reaches z0 first)
+  int zf0, zf1;
+  full_range(z0, zc_last + 1, zf0, zf1);
   prefetch_ids(zc_first);
   load_layer(zc_first);
+  // RS: the range's first offsets ride behind the first coordinates and are
+  // settled below, behind the second layer's (in-order returns: no wait of
+  // their own), so no loop head inherits a wait for them
+  if constexpr (RS) load_run_bases(zf0);
+  // the unit's first two layers in one batch (a second register set, free
+  // here: one round trip instead of load, stage, load); CANON: the second
+  // layer's ids are still on their way, its coordinates follow the staging
+  double pre1[2][3];
+  if constexpr (!CANON) load_layer_to(zc_first + 1, pre1);
   store_layer(zc_first & 1);
-  prefetch_ids(zc_first + 1);
-  load_layer(zc_first + 1);
-  prefetch_ids(zc_first + 2);
+  if constexpr (CANON) {
+    prefetch_ids(zc_first + 1);
+    load_layer(zc_first + 1);
+    prefetch_ids(zc_first + 2);
+  }
+  else {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int d = 0; d < 3; ++d) pre[h][d] = pre1[h][d];
+  }
   if constexpr (NCZ == 1) {  // the bottom layer into the corner registers before the top overwrites it
     wave_lds_order();
     prime_corners(zc_first);
@@ -1012,6 +1059,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   wave_lds_order();
   if constexpr (CARRY && NCZ == 2) prime_corners(zc_first);
   settle_ids();
+  double* run_base[kRun] = {};  // RS: where x-run q's first value goes on the range's next layer
+  if constexpr (RS) {
+    asm volatile("" : "+v"(rs_rb));
+#pragma unroll
+    for (int q = 0; q < kRun; ++q) run_base[q] = vals + lane_i64(rs_rb, kRun * q);
+  }
   int zc = zc_first;
   if (zc < z0) {  // the cube layer below the segment: its top corners only, no flush
     next_layer(zc + 2);
@@ -1049,8 +1102,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   // the layers below the complete range, the range, the layers above it: the
   // general loop is compiled once and entered twice (ph), the complete-layer
   // loop between its two passes
-  int zf0, zf1;
-  full_range(zc, zc_last + 1, zf0, zf1);
 #pragma nounroll
   for (int ph = 0; ph < 2; ++ph) {
     const int zend = ph == 0 ? zf0 : zc_last + 1;
@@ -1058,10 +1109,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     for (; zc < zend; ++zc) layer_step(zc, flush);
     if constexpr (!CANON) {
       if (ph == 0) {
+        if constexpr (RS) {
+          // the complete range without offset loads (a loop of its own, so the
+          // one below is the parent's when the structure has no constant stride)
+          if (g.row_stride != 0) {
+#pragma nounroll
+            for (; zc < zf1; ++zc) {
+              pf_r = layer_base(zc) + row_xy;  // zf0 <= zc < zf1: inside the segment
+              if constexpr (RHS_ADD) pf_rhs = rhs[pf_r];
+              if constexpr ((DIAG & 16) != 0) next_layer(zc + 2);
+              wave_lds_order();
+              cubes(zc);
+              if constexpr ((DIAG & 16) == 0) next_layer(zc + 2);
+              wave_lds_order();
+              if constexpr (!(DIAG & 8)) flush_full(zc, run_base);
+              store_layer(zc & 1);
+#pragma unroll
+              for (int q = 0; q < kRun; ++q) run_base[q] += g.row_stride;
+            }
+          }
+        }
 #pragma nounroll
         for (; zc < zf1; ++zc)
           layer_step(zc, [&](int z) {
-            if constexpr (!(DIAG & 8)) flush_full(z);
+            if constexpr (!(DIAG & 8)) flush_full(z, nullptr);
           });
       }
     }
@@ -1191,25 +1262,31 @@ __global__ __launch_bounds__(64) void k_cube_unstage(int64_t n, const int64_t* _
   }
 }
 
-}  // namespace
-
-bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
+// cube_row_stride's check: rows l in [l0, l1) of nodes-per-layer L, every node
+// xy: is the row's offset on layer l + 1 the one on layer l plus C?
+__global__ void k_row_stride_check(const int64_t* __restrict__ rows, int64_t L, int64_t l0, int64_t l1, int64_t C,
+                                   int32_t* __restrict__ bad)
 {
-  const Mesh& m = *b.mesh;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (l1 - l0) * L) return;
+  const int64_t r = l0 * L + i;
+  if (rows[r + L] - rows[r] != C) *bad = 1;
+}
+
+// the lattice the cube kernel walks on mesh m with structure S (the fields that
+// do not depend on the launch); false: not a mesh for it
+bool cube_lattice_geom(const Mesh& m, const Structure& S, int nb_dof, CubeGeom& g, bool& canon)
+{
   const StructuredInfo& st = m.st;
-  Structure& S = b.s;
-  const char* ce = variant("AFEM_ASSEMBLY_CUBES");  // 0: the strip / stencil kernels
-  if ((ce && atoi(ce) == 0) || m.nv != 4 || b.nb_dof != 1) return false;
+  if (m.nv != 4 || nb_dof != 1) return false;
   // a generator box (or z-slab of one), a lattice of Kuhn cubes in a natural
   // numbering (lexicographic in some axis order: the plain instance, with the
   // lattice axes in that order -- the kernel's geometry reads the real
   // coordinates, and the cube's 6 tets do not depend on the axis order), or
   // one in any other numbering (the caller's maps)
   const bool natural = S.cube_natural;
-  const bool canon = !natural && S.canon && S.cube_ok;
+  canon = !natural && S.canon && S.cube_ok;
   if (!canon && !natural && (!st.valid || st.dim != 3 || S.canon || st.lx > 0 || st.ly > 0 || st.n < 1)) return false;
-  Ctx& ctx = *m.ctx;
-  CubeGeom g{};
   if (canon || natural) {
     const int64_t* Lc = natural ? S.nat_L : S.cube_L;
     g.npx = (int)Lc[0];
@@ -1234,6 +1311,60 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
   if (g.n_own_layers <= 0 || g.nzc < 1 || g.npx < 2 || g.npy < 2) return false;
   g.tx = (g.npx + kRun - 1) / kRun;
   g.ty = (g.npy + kRun - 1) / kRun;
+  return true;
+}
+
+}  // namespace
+
+// Structure::cube_row_stride, once per structure (build_structure).  The node
+// layers a unit's complete range can hold are z in [k0 + 1, min(k1, nzc)):
+// owned, so local layers l = z - k0 in [1, lmax), consecutive.  The stride is
+// the constant C with rows[(l + 1) L + xy] = rows[l L + xy] + C for every such
+// pair of layers and every xy of the layer (C = rows[2 L] - rows[L]; with one
+// such layer there is no pair, and C is never added to an offset that is
+// used); 0 when there is no such layer, the lattice is a canonical one, or the
+// device finds a pair that differs.
+void cube_row_stride(const Mesh& m, Structure& S, int nb_dof)
+{
+  S.cube_row_stride = 0;
+  CubeGeom g{};
+  bool canon = false;
+  if (!cube_lattice_geom(m, S, nb_dof, g, canon) || canon) return;
+  const int64_t lmax = std::min(g.k1, g.nzc) - g.k0;
+  if (lmax < 2 || lmax * g.L > S.n_rows) return;  // (every such layer's rows, and the one behind them, exist)
+  Ctx& ctx = *m.ctx;
+  int64_t h[2] = { 0, 0 };
+  AFEM_HIP(hipMemcpyAsync(&h[0], S.row_ptr.p + g.L, sizeof(int64_t), hipMemcpyDeviceToHost, ctx.stream));
+  AFEM_HIP(hipMemcpyAsync(&h[1], S.row_ptr.p + 2 * g.L, sizeof(int64_t), hipMemcpyDeviceToHost, ctx.stream));
+  ctx.sync();
+  const int64_t C = h[1] - h[0];
+  if (C <= 0) return;
+  int32_t bad = 0;
+  const int64_t n_pairs = (lmax - 2) * g.L;  // layers l, l + 1 with 1 <= l, l + 1 < lmax
+  if (n_pairs > 0) {
+    DevBuf<int32_t> flag;
+    flag.alloc(1);
+    AFEM_HIP(hipMemsetAsync(flag.p, 0, flag.bytes(), ctx.stream));
+    hipLaunchKernelGGL(k_row_stride_check, dim3(grid_for(n_pairs, 256)), dim3(256), 0, ctx.stream, S.row_ptr.p, g.L,
+                       (int64_t)1, lmax - 1, C, flag.p);
+    AFEM_LAUNCHED();
+    AFEM_HIP(hipMemcpyAsync(&bad, flag.p, sizeof(bad), hipMemcpyDeviceToHost, ctx.stream));
+    ctx.sync();
+  }
+  S.cube_row_stride = bad ? 0 : C;
+}
+
+bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
+{
+  const Mesh& m = *b.mesh;
+  Structure& S = b.s;
+  const char* ce = variant("AFEM_ASSEMBLY_CUBES");  // 0: the strip / stencil kernels
+  if (ce && atoi(ce) == 0) return false;
+  CubeGeom g{};
+  bool canon = false;
+  if (!cube_lattice_geom(m, S, b.nb_dof, g, canon)) return false;
+  Ctx& ctx = *m.ctx;
+  g.row_stride = S.cube_row_stride;
   const char* ze = variant("AFEM_CUBES_ZS");
   // z segment: ~n/16 layers (C2 n = 215: 13, C4 n = 463: 29; r04x: zs 12 0.645 ms
   // vs zs 8 0.649 at C2, zs 32 6.38 vs zs 24 6.81 ms at C4)
@@ -1263,33 +1394,39 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
   // and the y = 1 face's with lane + 8 (AFEM_CUBES_YEX=0: not; needs the x exchange)
   const char* ye = variant("AFEM_CUBES_YEX");
   const bool yex = canon || (xex && !(ye && atoi(ye) == 0));
-#define AFEM_CUBES_K(S, C, X, Y, N)                                                                                  \
-  (rhs ? (rhs_add ? &k_assemble_cubes<S, C, X, Y, N, true, true> : &k_assemble_cubes<S, C, X, Y, N, true, false>)    \
-       : &k_assemble_cubes<S, C, X, Y, N, false, false>)
+#define AFEM_CUBES_K(S, C, X, Y, N, D)                                                                               \
+  (rhs ? (rhs_add ? &k_assemble_cubes<S, C, X, Y, N, true, true, D> : &k_assemble_cubes<S, C, X, Y, N, true, false, D>) \
+       : &k_assemble_cubes<S, C, X, Y, N, false, false, D>)
   const char* de = variant("AFEM_CUBES_V");
   const int diag = de ? atoi(de) : kCubesV;
-  // canonical structures: the staged instance (below), or the single-pass one (V without 1024)
-  auto* kern = canon ? (rhs ? (rhs_add ? &k_assemble_cubes<64, true, true, true, true, true, true, kCubesV & ~1024>
-                                       : &k_assemble_cubes<64, true, true, true, true, true, false, kCubesV & ~1024>)
-                            : &k_assemble_cubes<64, true, true, true, true, false, false, kCubesV & ~1024>)
-               : carry ? (xex ? (yex ? (s49 ? AFEM_CUBES_K(49, true, true, true, false)
-                                            : AFEM_CUBES_K(64, true, true, true, false))
-                                     : AFEM_CUBES_K(64, true, true, false, false))
-                              : AFEM_CUBES_K(64, true, false, false, false))
-                       : (s49 ? AFEM_CUBES_K(49, false, false, false, false) : AFEM_CUBES_K(64, false, false, false, false));
+  // canonical structures: the staged instance (below), or the single-pass one (V without 1024).
+  // The headline instance (64 rows, carry, both exchanges) takes the default V, or the
+  // same with or without bit 4096 as AFEM_CUBES_V says (every RHS mode); the canonical
+  // ones and the box instances without an exchange or with 49-row planes stay at the V
+  // they were built with (no bit 4096)
+  constexpr int kB = kCubesBase;
+  auto* kern = canon ? AFEM_CUBES_K(64, true, true, true, true, kB & ~1024)
+               : carry ? (xex ? (yex ? (s49 ? AFEM_CUBES_K(49, true, true, true, false, kB)
+                                            : ((diag & 4096) ? AFEM_CUBES_K(64, true, true, true, false, kB | 4096)
+                                                             : AFEM_CUBES_K(64, true, true, true, false, kB)))
+                                     : AFEM_CUBES_K(64, true, true, false, false, kB))
+                              : AFEM_CUBES_K(64, true, false, false, false, kB))
+                       : (s49 ? AFEM_CUBES_K(49, false, false, false, false, kB)
+                              : AFEM_CUBES_K(64, false, false, false, false, kB));
 #undef AFEM_CUBES_K
   // AFEM_CUBES_V: another variant of the headline instance (generator boxes and
   // natural lattices, RHS set) or of the canonical one (RHS set)
-  if (diag != kCubesV && carry && xex && yex && rhs && !rhs_add) {
+  if (diag != (kB | 4096) && diag != kB && carry && xex && yex && rhs && !rhs_add) {
     switch (diag) {
 #define AFEM_CUBES_D(D)                                                                                              \
   case D:                                                                                                            \
-    kern = canon ? &k_assemble_cubes<64, true, true, true, true, true, false, (D) & ~1024>                          \
+    kern = canon ? &k_assemble_cubes<64, true, true, true, true, true, false, (D) & ~(1024 | 4096)>                 \
                  : &k_assemble_cubes<64, true, true, true, false, true, false, D>;                                  \
     break;
-      AFEM_CUBES_D(0) AFEM_CUBES_D(112) AFEM_CUBES_D(kCubesV | 1) AFEM_CUBES_D(kCubesV | 4)
-      AFEM_CUBES_D(kCubesV | 8) AFEM_CUBES_D(kCubesV | 2) AFEM_CUBES_D(kCubesV & ~512) AFEM_CUBES_D(kCubesV & ~1024)
-      AFEM_CUBES_D(kCubesV & ~32) AFEM_CUBES_D(kCubesV & ~2048) AFEM_CUBES_D(kCubesV & ~(1024 | 2048))
+      AFEM_CUBES_D(0) AFEM_CUBES_D(112) AFEM_CUBES_D(kB | 1) AFEM_CUBES_D(kB | 4)
+      AFEM_CUBES_D(kB | 8) AFEM_CUBES_D(kB | 2) AFEM_CUBES_D(kB & ~512) AFEM_CUBES_D(kB & ~1024)
+      AFEM_CUBES_D(kB & ~32) AFEM_CUBES_D(kB & ~2048) AFEM_CUBES_D(kB & ~(1024 | 2048))
+      AFEM_CUBES_D(kB | 4096 | 1) AFEM_CUBES_D(kB | 4096 | 4) AFEM_CUBES_D(kB | 4096 | 8)
 #undef AFEM_CUBES_D
       default: break;
     }
@@ -1311,14 +1448,14 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
     }
     if (b.cube_stage.n != (size_t)(16 * n_lat)) b.cube_stage.alloc(16 * n_lat);
     cc.stage = b.cube_stage.p;
-    kern = &k_assemble_cubes<64, true, true, true, true, false, false, kCubesV | 1024>;
-    if (diag != kCubesV) {
+    kern = &k_assemble_cubes<64, true, true, true, true, false, false, kCubesBase | 1024>;
+    if (diag != (kCubesBase | 4096) && diag != kCubesBase) {
       switch (diag) {
 #define AFEM_CUBES_S(D)                                                                                              \
   case D:                                                                                                            \
     kern = &k_assemble_cubes<64, true, true, true, true, false, false, D>;                                          \
     break;
-        AFEM_CUBES_S(kCubesV | 1024 | 1) AFEM_CUBES_S(kCubesV | 1024 | 4) AFEM_CUBES_S(kCubesV & ~2048)
+        AFEM_CUBES_S(kCubesBase | 1024 | 1) AFEM_CUBES_S(kCubesBase | 1024 | 4) AFEM_CUBES_S(kCubesBase & ~2048)
 #undef AFEM_CUBES_S
         default: break;
       }

@@ -2223,10 +2223,9 @@ bool canonical_lattice(Mesh& m, Structure& s)
 
 }  // namespace
 
-void build_structure(Mesh& m, Structure& s, int nb_dof)
+// a scalar tet mesh given as arrays whose nodes form a lattice: which kind
+static void array_lattice_kind(Mesh& m, Structure& s)
 {
-  build_structure_impl(m, s);
-  if (!(nb_dof == 1 && s.lattice && m.nv == 4 && m.dim == 3 && m.n_nodes == m.n_own)) return;
   // an array-fed Kuhn lattice in a natural numbering: the cube kernel as on
   // the generator's box (AFEM_CUBE_NATURAL=0: not)
   const char* ne = variant("AFEM_CUBE_NATURAL");
@@ -2250,6 +2249,13 @@ void build_structure(Mesh& m, Structure& s, int nb_dof)
       }
     }
   }
+}
+
+void build_structure(Mesh& m, Structure& s, int nb_dof)
+{
+  build_structure_impl(m, s);
+  if (nb_dof == 1 && s.lattice && m.nv == 4 && m.dim == 3 && m.n_nodes == m.n_own) array_lattice_kind(m, s);
+  cube_row_stride(m, s, nb_dof);  // the cube kernel's, once the lattice kind is known
 }
 
 }  // namespace afem

@@ -254,6 +254,9 @@ typedef struct afem_bsr_stats {
                                3 a Kuhn lattice in any other numbering (canonical maps); 0 none */
   int32_t cube_axes;        /* cube_lattice 2: the numbering's axis order, fastest first, as
                                a0 + 3 a1 + 9 a2 (x + Lx (y + Ly z): 0 + 3 + 18 = 21) */
+  int64_t cube_row_stride;  /* cube_lattice 1 or 2: the constant by which a row's first-value offset grows
+                               from one node layer to the next over the layers whose rows can all be
+                               complete (the cube kernel then loads no row offsets there); 0: none */
 } afem_bsr_stats;
 #define AFEM_KERNEL_NONE 0
 #define AFEM_KERNEL_STRIP 1          /* scalar row-strip kernel (uniform + general instances) */

@@ -260,7 +260,9 @@ def main() -> int:
     for name, lo, hi in funcs:
         g = NAME.search(name).groups()
         default = g[:4] == ("64", "1", "1", "1") and ((g[4] == "0" and int(g[7]) == vdef)
-                                                     or (g[4] == "1" and int(g[7]) == (vdef | 1024) and g[5] == "0"))
+                                                     # (the canonical instances never carry bit 4096)
+                                                     or (g[4] == "1" and int(g[7]) == ((vdef & ~4096) | 1024)
+                                                         and g[5] == "0"))
         if not (show_all or default):
             continue
         b = report(lines, name, lo, hi, print)
