@@ -87,7 +87,10 @@ class BsrStats(ctypes.Structure):
                 ("stencil_sig", ctypes.c_int32), ("shared_strip_slices", ctypes.c_int64),
                 ("uniform_instance_slices", ctypes.c_int64), ("general_slices", ctypes.c_int64),
                 ("cube_lattice", ctypes.c_int32), ("cube_axes", ctypes.c_int32),
-                ("cube_row_stride", ctypes.c_int64)]
+                ("cube_row_stride", ctypes.c_int64), ("cube_units", ctypes.c_int64),
+                ("cube_unit_records", ctypes.c_int64), ("cube_unit_table", ctypes.c_void_p),
+                ("cube_xcd_cost_spread", ctypes.c_double), ("cube_sched", ctypes.c_int32),
+                ("reserved0", ctypes.c_int32)]
 
 
 class SolverOpts(ctypes.Structure):

@@ -295,6 +295,15 @@ class BSRFormat:
         call("afem_bsr_get_stats", self.h, ctypes.byref(s))
         return {k: getattr(s, k) for k, _ in s._fields_}
 
+    def cube_unit_table(self, ctx: "Context") -> np.ndarray:
+        """The cube kernel's unit table as of the last assembly, downloaded:
+        one row {column x, column y, z0, z1} per workgroup (afem_bsr_stats)."""
+        s = self.stats()
+        w = ctx.to_host(s["cube_unit_table"] or 0, 2 * s["cube_unit_records"], np.uint32)
+        w = w.reshape(-1, 2).astype(np.int64)
+        z0 = w[:, 1] & 0xFFFFFF
+        return np.stack([w[:, 0] & 0xFFFF, w[:, 0] >> 16, z0, z0 + (w[:, 1] >> 24)], 1)
+
     def functor_plan(self) -> dict:
         """The cell-unit plan of the generic element-functor kernel
         (afem_bsr_functor_plan; built at the first call)."""

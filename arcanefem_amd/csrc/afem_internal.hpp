@@ -300,6 +300,17 @@ struct Structure {
   // a cube unit's complete range can hold (cubes.hip cube_row_stride, checked
   // on the device when the structure is built); 0: none, or not one constant
   int64_t cube_row_stride = 0;
+  // the cube kernel's unit table (cubes.hip build_cube_units, built at the first
+  // assembly and again only when the plan's parameters -- cube_units_key --
+  // change): one 8-byte record (column x | column y << 16, z0 | (z1 - z0) << 24)
+  // per block of the grid, cube_units_n of them, cube_units_real not padding; the plan that built it
+  // (1: cost-balanced XCD regions, most expensive first; 0: lattice order, equal
+  // counts) and its modelled cost per XCD, largest over smallest
+  DevBuf<uint32_t> cube_units;
+  int64_t cube_units_n = 0, cube_units_real = 0;
+  int cube_units_sched = 0;
+  double cube_xcd_spread = 0.0;
+  int64_t cube_units_key[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
   DevBuf<int32_t> cube_phys;
   DevBuf<int64_t> cube_rb;
   DevBuf<uint64_t> cube_slot;

@@ -694,6 +694,12 @@ int afem_bsr_get_stats(afem_bsr* b, afem_bsr_stats* st)
   st->general_slices = b->s.n_ms + b->s.n_mb;
   st->cube_axes = b->s.cube_natural ? b->s.nat_axes[0] + 3 * b->s.nat_axes[1] + 9 * b->s.nat_axes[2] : 0;
   st->cube_row_stride = b->s.cube_row_stride;
+  st->cube_units = b->s.cube_units_real;
+  st->cube_unit_records = b->s.cube_units_n;
+  st->cube_unit_table = b->s.cube_units.p;
+  st->cube_xcd_cost_spread = b->s.cube_xcd_spread;
+  st->cube_sched = b->s.cube_units_sched;
+  st->reserved0 = 0;
   st->last_kernel = b->last_kernel;
   API_END
 }

@@ -40,6 +40,20 @@
 // 49-row planes or without the dummy rows keep the adds into zeroed
 // [15][STRIDE] planes described above.  Same bits either way.
 //
+// Which block runs which unit comes from a table (Structure::cube_units,
+// build_cube_units, built once per structure and plan): block bid, on XCD
+// bid & 7, loads record bid -- one 8-byte scalar load instead of the div / mod
+// of the block index.  Each XCD takes a contiguous run of the units in lattice
+// order (x fastest, then y, then z segment: neighbouring units share their halo
+// coordinates in one L2) cut by modelled cost, not by count, and runs it most
+// expensive unit first (columns on an x / y face, whose every layer takes the
+// general flush, cost 1.6 x an interior column; the box's short last segment
+// 0.65 x), so an XCD's slots go idle behind its cheapest units and all XCDs
+// finish together: measured with the AFEM_WAVE_TIMES build
+// (tools/cube_wave_times.py).  AFEM_CUBES_SCHED=0 builds
+// the table in lattice order with equal counts per XCD, the mapping computed in
+// the kernel up to r09a.  Same units, same arithmetic: same bits.
+//
 // Applies to meshes from afem_mesh_create_structured (3D, NB_DOF 1, any
 // z-slab: the columns follow the local numbering -- owned layers, then the
 // ghost layer below, then above -- so the sorted column order of a row next to
@@ -53,7 +67,9 @@
 #include "afem_internal.hpp"
 
 #include <algorithm>
+#include <cstring>
 #include <limits>
+#include <vector>
 
 // the 64-row instances cannot reach the 3-waves register target (their LDS
 // allows 2 per SIMD): the compiler says so for each; expected
@@ -81,7 +97,43 @@ __device__ __forceinline__ double precip(double a)
   return fma(r, e, r);
 }
 
+// one unit of the kernel's grid (build_cube_units): the column (cx, cy) of
+// 7 x 7 rows over the owned node layers [z0, z1); z0 == z1: a padding record,
+// its block ends at once.  In Structure::cube_units a record is 8 bytes,
+// cx | cy << 16 and z0 | (z1 - z0) << 24 (16 bytes, one int each, compiled to 56
+// spilled scalar registers in the headline instance against 49 with these 8 or
+// with the arithmetic the table replaces: the kernel sits at the 106-SGPR cap)
+struct CubeUnit {
+  int32_t cx, cy, z0, z1;
+};
+constexpr int kUnitMaxColumns = 1 << 16, kUnitMaxLayer = 1 << 24, kUnitMaxLayers = 255;
+
+#ifdef AFEM_WAVE_TIMES
+// diagnostic build only (make EXTRA=-DAFEM_WAVE_TIMES OBJDIR=build_wt
+// OUT=../libafem_wt.so; tools/cube_wave_times.py): start / end realtime stamps
+// and the block index of every workgroup of the cube kernel, the first and the
+// last 16 384 blocks of the grid (a grid of up to 32 768 blocks: all of them)
+constexpr unsigned kCubeWtHalf = 16384;
+__device__ unsigned long long afem_cube_wave_t[3 * 2 * kCubeWtHalf];
+extern "C" int afem_debug_cube_wave_times(unsigned long long* out, int n)
+{
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(afem_cube_wave_t), sizeof(unsigned long long) * (size_t)(3 * n));
+}
+#define AFEM_CWT(i, v)                                                                               \
+  do {                                                                                               \
+    const unsigned b_ = blockIdx.x, back_ = gridDim.x - b_;                                          \
+    if (threadIdx.x == 0 && (b_ < kCubeWtHalf || back_ <= kCubeWtHalf)) {                            \
+      const unsigned s_ = b_ < kCubeWtHalf ? b_ : 2 * kCubeWtHalf - back_;                           \
+      afem_cube_wave_t[3 * s_ + (i)] = (v);                                                          \
+      afem_cube_wave_t[3 * s_ + 2] = b_;                                                             \
+    }                                                                                                \
+  } while (0)
+#else
+#define AFEM_CWT(i, v) (void)0
+#endif
+
 struct CubeGeom {
+  const uint2* units;  // the grid's unit records, one per block
   int npx, npy;      // nodes per x line, per y line
   int nzc;           // cells of the global box in z (node layers 0..nzc)
   int k0, k1;        // owned node layers [k0, k1)
@@ -262,18 +314,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   constexpr int NCZ = CARRY ? 1 : 2;
   __shared__ double cz[NCZ][3][kCol * kCol];
   const int lane = threadIdx.x;
-  // XCD-aware: blocks go round-robin over the 8 XCDs; XCD x takes the x-th
-  // contiguous eighth of the units (x fastest, then y, then segments)
-  const int64_t n_units = (int64_t)g.tx * g.ty * g.ns;
-  const int64_t bid = blockIdx.x;
-  const int64_t qq = n_units >> 3, rem = n_units & 7, xc = bid & 7, jj = bid >> 3;
-  const int64_t u = xc * qq + (xc < rem ? xc : rem) + jj;
-  const int utx = (int)(u % g.tx);
-  const int uty = (int)((u / g.tx) % g.ty);
-  const int seg = (int)(u / ((int64_t)g.tx * g.ty));
-  const int cx0 = kRun * utx, cy0 = kRun * uty;
-  const int z0 = g.k0 + seg * g.zs;
-  const int z1 = min(z0 + g.zs, g.k1);
+  // the unit of this block: one scalar load of its record from the structure's
+  // unit table (build_cube_units below: blocks go round-robin over the 8 XCDs,
+  // so record bid is XCD bid & 7's (bid >> 3)-th); a padding record is empty
+  const uint2 rec = g.units[blockIdx.x];
+  const int z0 = (int)(rec.y & 0xffffffu), z1 = z0 + (int)(rec.y >> 24);
+  if (z0 >= z1) return;
+  AFEM_CWT(0, __builtin_amdgcn_s_memrealtime());
+  const int cx0 = kRun * (int)(rec.x & 0xffffu), cy0 = kRun * (int)(rec.x >> 16);
   const int zc_first = max(z0 - 1, 0);
   const int zc_last = min(z1 - 1, g.nzc - 1);  // cube layer zc: node layers zc, zc + 1
 
@@ -1145,6 +1193,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     }
     flush(zc_last + 1);
   }
+  AFEM_CWT(1, __builtin_amdgcn_s_memrealtime());
 }
 
 // the staged canonical path's maps, per lattice node i (caller row phys[i]):
@@ -1314,6 +1363,138 @@ bool cube_lattice_geom(const Mesh& m, const Structure& S, int nb_dof, CubeGeom& 
   return true;
 }
 
+// ---- the unit table.  The hardware hands out blocks in index order, block bid
+// to XCD bid & 7, and a CU takes the next block when a slot frees, so the order
+// of the records is a list schedule.  A unit's cost is modelled from what its
+// walk runs (unit start, the cube layer below its segment, complete layers,
+// general layers, the box's top layer), in units of one complete layer: the
+// constants are the least-squares fit of the unit durations measured with the
+// lattice-order table at C2 (profiles/r10a_cube_wave_times_parent.txt).
+// (fit at C2, us: start 1.86, below 2.43, complete 2.99, general 4.99, top 2.69)
+constexpr double kCostStart = 0.62;
+constexpr double kCostBelow = 0.81;
+constexpr double kCostFull = 1.0;
+constexpr double kCostGeneral = 1.67;
+constexpr double kCostTop = 0.90;
+constexpr int kXcds = 8;
+
+// what the kernel's walk runs on the unit (the kernel's own zc_first, zc_last, full_range)
+struct CubeUnitWork {
+  int below, full, general, top;
+};
+CubeUnitWork cube_unit_work(const CubeGeom& g, bool canon, const CubeUnit& u)
+{
+  const int cx0 = kRun * u.cx, cy0 = kRun * u.cy;
+  const int zc_first = std::max(u.z0 - 1, 0), zc_last = std::min(u.z1 - 1, g.nzc - 1);
+  const bool xy_full = cx0 >= 1 && cx0 + kRun <= g.npx - 1 && cy0 >= 1 && cy0 + kRun <= g.npy - 1;
+  const int zhi = zc_last + 1;
+  int zf0 = zhi, zf1 = zhi;
+  if (!canon && xy_full && g.full_flush) {
+    zf0 = std::min(std::max(u.z0, g.k0 + 1), zhi);
+    zf1 = std::max(std::min(zhi, g.nzc), zf0);
+  }
+  CubeUnitWork w;
+  w.below = zc_first < u.z0 ? 1 : 0;
+  w.full = zf1 - zf0;
+  w.general = std::max(zhi - u.z0, 0) - w.full;
+  w.top = (zhi >= u.z0 && zhi < u.z1) ? 1 : 0;
+  return w;
+}
+double cube_unit_cost(const CubeGeom& g, bool canon, const CubeUnit& u)
+{
+  const CubeUnitWork w = cube_unit_work(g, canon, u);
+  return kCostStart + kCostBelow * w.below + kCostFull * w.full + kCostGeneral * w.general + kCostTop * w.top;
+}
+
+// Structure::cube_units for the plan (g, canon, sched, band_rows, pat), kept
+// until the plan changes.  The units in lattice order are u = x + tx (y + ty
+// segment); the segments' lengths are pat's, repeated from k0 up to k1 (one
+// length: uniform segments, the default).
+// sched 0: XCD x takes the x-th contiguous eighth of them by count, in that
+// order; the grid is the units (the mapping the kernel computed up to r09a).
+// sched 1: XCD x takes the x-th contiguous run by modelled cost (a unit goes to
+// the eighth its cost's midpoint falls in: neighbouring units still share their
+// halo coordinates in one L2), and runs it most expensive unit first, ties in
+// lattice order, so what is left when an XCD's slots start to go idle is its
+// cheapest units.  The runs differ in count: the grid is 8 x the longest, the
+// shorter lists end in padding records.  band_rows > 0 (AFEM_CUBES_BAND, a
+// measurement knob) sorts within bands of that many y-rows of units only: the
+// whole-run sort reads 5 % more coordinates from HBM at C2 (FETCH_SIZE; 1 % of
+// the launch's bytes) and is the faster one all the same.
+void build_cube_units(const Mesh& m, Structure& S, const CubeGeom& g, bool canon, int sched, int band_rows,
+                      const std::vector<int>& pat)
+{
+  int64_t pat_key = 0;
+  for (int p : pat) pat_key = pat_key * 256 + p;
+  const int64_t key[12] = { g.npx, g.npy, g.nzc, g.k0, g.k1, pat_key, (int64_t)pat.size(),
+                            band_rows, g.n_own_layers, canon ? 1 : 0, g.full_flush, sched };
+  if (S.cube_units.p && std::equal(key, key + 12, S.cube_units_key)) return;
+  std::vector<int> cuts{ g.k0 };  // the segments' first layers, and k1
+  for (size_t i = 0; cuts.back() < g.k1; ++i) cuts.push_back(std::min(cuts.back() + pat[i % pat.size()], g.k1));
+  const int64_t n_col = (int64_t)g.tx * g.ty, n_units = n_col * (int64_t)(cuts.size() - 1);
+  AFEM_REQUIRE(n_units < (int64_t(1) << 31), AFEM_ERR_LIMIT, "cube kernel: too many units");
+  std::vector<CubeUnit> units((size_t)n_units);
+  std::vector<double> cost((size_t)n_units);
+  double total = 0.0;
+  for (int64_t u = 0; u < n_units; ++u) {
+    const int seg = (int)(u / n_col);
+    units[u] = CubeUnit{ (int32_t)(u % g.tx), (int32_t)((u / g.tx) % g.ty), cuts[seg], cuts[seg + 1] };
+    cost[u] = cube_unit_cost(g, canon, units[u]);
+    total += cost[u];
+  }
+  std::vector<int64_t> list[kXcds];
+  if (sched) {
+    double cum = 0.0;
+    for (int64_t u = 0; u < n_units; ++u) {
+      const int x = std::min(kXcds - 1, (int)(kXcds * (cum + 0.5 * cost[u]) / total));
+      list[x].push_back(u);
+      cum += cost[u];
+    }
+    const int64_t band = band_rows > 0 ? (int64_t)band_rows * g.tx : n_units;
+    for (auto& l : list)
+      std::stable_sort(l.begin(), l.end(), [&](int64_t a, int64_t b) {
+        return a / band != b / band ? a / band < b / band : cost[a] > cost[b];
+      });
+  }
+  else {
+    const int64_t qq = n_units / kXcds, rem = n_units % kXcds;
+    for (int x = 0; x < kXcds; ++x) {
+      const int64_t first = x * qq + std::min<int64_t>(x, rem), count = qq + (x < rem ? 1 : 0);
+      for (int64_t j = 0; j < count; ++j) list[x].push_back(first + j);
+    }
+  }
+  size_t longest = 0;
+  double cmax = 0.0, cmin = std::numeric_limits<double>::max();
+  for (const auto& l : list) {
+    longest = std::max(longest, l.size());
+    if (l.empty()) continue;  // fewer units than XCDs: the spread is over the XCDs that have some
+    double c = 0.0;
+    for (int64_t u : l) c += cost[u];
+    cmax = std::max(cmax, c);
+    cmin = std::min(cmin, c);
+  }
+  const int64_t n_rec = sched ? (int64_t)kXcds * (int64_t)longest : n_units;
+  AFEM_REQUIRE(n_rec < (int64_t(1) << 31), AFEM_ERR_LIMIT, "cube kernel: too many units");
+  AFEM_REQUIRE(g.tx <= kUnitMaxColumns && g.ty <= kUnitMaxColumns && g.k1 < kUnitMaxLayer,
+               AFEM_ERR_LIMIT, "cube kernel: a unit does not fit its record");
+  auto packed = [](const CubeUnit& u) {
+    return uint2{ (uint32_t)u.cx | (uint32_t)u.cy << 16, (uint32_t)u.z0 | (uint32_t)(u.z1 - u.z0) << 24 };
+  };
+  std::vector<uint2> table((size_t)n_rec, packed(CubeUnit{ 0, 0, g.k0, g.k0 }));
+  for (int x = 0; x < kXcds; ++x)
+    for (size_t j = 0; j < list[x].size(); ++j) table[kXcds * j + x] = packed(units[list[x][j]]);
+  Ctx& ctx = *m.ctx;
+  S.cube_units.alloc(2 * (size_t)n_rec);
+  AFEM_HIP(hipMemcpyAsync(S.cube_units.p, table.data(), sizeof(uint2) * (size_t)n_rec, hipMemcpyHostToDevice,
+                          ctx.stream));
+  ctx.sync();
+  S.cube_units_n = n_rec;
+  S.cube_units_real = n_units;
+  S.cube_units_sched = sched;
+  S.cube_xcd_spread = cmax / cmin;
+  std::copy(key, key + 12, S.cube_units_key);
+}
+
 }  // namespace
 
 // Structure::cube_row_stride, once per structure (build_structure).  The node
@@ -1368,8 +1549,14 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
   const char* ze = variant("AFEM_CUBES_ZS");
   // z segment: ~n/16 layers (C2 n = 215: 13, C4 n = 463: 29; r04x: zs 12 0.645 ms
   // vs zs 8 0.649 at C2, zs 32 6.38 vs zs 24 6.81 ms at C4)
-  g.zs = std::max(1, ze ? atoi(ze) : std::min(48, std::max(8, std::max(g.npx, g.npy) / 16)));
-  g.ns = (g.n_own_layers + g.zs - 1) / g.zs;
+  // AFEM_CUBES_ZS: one length, or a list "20/7" repeated up the box (graded segments: swept in
+  // r10a, C2 within 1.4 % of the uniform default, not adopted)
+  std::vector<int> pat;
+  for (const char* p = ze; p && *p && pat.size() < 7; p = strchr(p, '/') ? strchr(p, '/') + 1 : "")
+    pat.push_back(std::min(kUnitMaxLayers, std::max(1, atoi(p))));
+  if (pat.empty()) pat.push_back(std::min(48, std::max(8, std::max(g.npx, g.npy) / 16)));
+  g.zs = *std::max_element(pat.begin(), pat.end());
+  g.ns = 0;
   g.s_coef = coef / 6.0;
   g.f_meas = f / 24.0;
   const char* fe = variant("AFEM_CUBES_FULL");
@@ -1378,8 +1565,12 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
   // there the outputs stay finite only if no flush reads a slot its layer did not write)
   const char* ie = variant("AFEM_CUBES_ACC_INIT");
   g.acc_init = (ie && (ie[0] == 'n' || ie[0] == 'N')) ? std::numeric_limits<double>::quiet_NaN() : 0.0;
-  const int64_t n_units = (int64_t)g.tx * g.ty * g.ns;
-  AFEM_REQUIRE(n_units < (int64_t(1) << 31), AFEM_ERR_LIMIT, "cube kernel: too many units");
+  // the unit table (built once per structure and plan): AFEM_CUBES_SCHED=0 keeps the
+  // lattice order and the equal-count eighths, for the A/B of the order alone
+  const char* sce = variant("AFEM_CUBES_SCHED");
+  const char* be = variant("AFEM_CUBES_BAND");
+  build_cube_units(m, S, g, canon, (sce && atoi(sce) == 0) ? 0 : 1, be ? std::max(0, atoi(be)) : 0, pat);
+  g.units = reinterpret_cast<const uint2*>(S.cube_units.p);
   // accumulator planes of 64 rows (19.3 KB of LDS, 8 waves per CU), or of 49
   // (AFEM_CUBES_STRIDE=49: 15.6 KB, 10 waves -- with the carry it spills: r04y)
   const char* se = variant("AFEM_CUBES_STRIDE");
@@ -1461,8 +1652,8 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
       }
     }
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)n_units), dim3(64), 0, ctx.stream, g, S.row_ptr.p, m.coords.p, b.values.p,
-                     rhs, cc);
+  hipLaunchKernelGGL(kern, dim3((unsigned)S.cube_units_n), dim3(64), 0, ctx.stream, g, S.row_ptr.p, m.coords.p,
+                     b.values.p, rhs, cc);
   AFEM_LAUNCHED();
   if (staged) {
     const int64_t n = S.n_rows;

@@ -257,6 +257,19 @@ typedef struct afem_bsr_stats {
   int64_t cube_row_stride;  /* cube_lattice 1 or 2: the constant by which a row's first-value offset grows
                                from one node layer to the next over the layers whose rows can all be
                                complete (the cube kernel then loads no row offsets there); 0: none */
+  int64_t cube_units;       /* the cube kernel's unit table as of its last launch (0 before the first):
+                               columns of 7 x 7 rows over a z segment, one per workgroup */
+  int64_t cube_unit_records;/* records of that table = workgroups of the launch: the units and, where
+                               the XCDs' lists differ in length, empty padding records (z0 == z1) */
+  const uint32_t* cube_unit_table; /* device memory, 2 uint32 per record: column x | column y << 16 (columns of
+                               7 rows), z0 | (z1 - z0) << 24 (owned node layers [z0, z1)); record i is run
+                               by workgroup i, on XCD i & 7; valid until the next assembly of this
+                               matrix (diagnostics and tests: afem_memcpy) */
+  double cube_xcd_cost_spread; /* modelled cost of the XCDs' unit lists, largest over smallest (over the
+                               XCDs that have units) */
+  int32_t cube_sched;       /* the table's plan: 1 XCD regions balanced by modelled cost, each run most
+                               expensive unit first; 0 lattice order, equal counts (AFEM_CUBES_SCHED=0) */
+  int32_t reserved0;
 } afem_bsr_stats;
 #define AFEM_KERNEL_NONE 0
 #define AFEM_KERNEL_STRIP 1          /* scalar row-strip kernel (uniform + general instances) */
