@@ -242,14 +242,41 @@ __device__ __forceinline__ void put(double* p, double v)
   else
     *p = v;
 }
+// two doubles as one 16-B access, at an 8-B aligned address (rows of 15 values) or a 16-B aligned one
+typedef double d2u8 __attribute__((ext_vector_type(2), aligned(8)));
+typedef double d2u16 __attribute__((ext_vector_type(2), aligned(16)));
+template <bool NT>
+__device__ __forceinline__ void put2(double* p, double a, double b)
+{
+  if constexpr (NT)
+    __builtin_nontemporal_store(d2u8{ a, b }, reinterpret_cast<d2u8*>(p));
+  else
+    *reinterpret_cast<d2u8*>(p) = d2u8{ a, b };
+}
+
+// which of the 15 Kuhn neighbours (bit o: offset o) of node (x, y, z) a lattice
+// of npx x npy nodes per layer, node layers 0..nzc, holds: branch-free (bitwise
+// ands of the comparisons), so a flush that uses it stays straight-line code
+__host__ __device__ __forceinline__ uint32_t presence_mask(int x, int y, int z, int npx, int npy, int nzc)
+{
+  uint32_t mask = 0;
+#pragma unroll
+  for (int o = 0; o < 15; ++o) {
+    const int xx = x + kOffX[o], yy = y + kOffY[o], zz = z + kOffZ[o];
+    const uint32_t in = (uint32_t)(xx >= 0) & (uint32_t)(yy >= 0) & (uint32_t)(xx < npx) & (uint32_t)(yy < npy) &
+                        (uint32_t)(zz >= 0) & (uint32_t)(zz <= nzc);
+    mask |= in << o;
+  }
+  return mask;
+}
+constexpr uint32_t kAllPresent = 0x7fffu;
 
 // HAS_RHS / RHS_ADD at compile time: each flush's global stores are then a
 // fixed, branch-free sequence.  That alone does not keep them in flight: the
 // wait for the next layer's coordinates counts past them (vmcnt(N)) only if
 // the loop body holds one flush and no branch around it (the z walk at the
 // end of the kernel; tools/loop_waits.py shows the compiled loops)
-// amdgpu_waves_per_eu(3): 168 VGPRs, with the 49-row planes' 15.6 KB of LDS
-// 10 waves per CU (the 64-row planes' 19.3 KB keep 8 whatever the registers)
+// (registers, LDS and occupancy: cube_waves below)
 // CANON: a lattice mesh in the caller's numbering (sparsity.hip canonical_lattice,
 // Structure::cube_*): the unit walks lattice indices; a node's coordinates
 // come through its caller id, a row's values go to the caller's row (first
@@ -292,12 +319,30 @@ struct CubeCanon {
 // scalar row bases in the complete-layer loop -- where the structure's row
 // offsets advance by one constant per layer (CubeGeom::row_stride != 0) that
 // loop loads no row offsets (RS in the kernel); measured in DESIGN.md §3.1e (r09a).
-constexpr int kCubesBase = 16 | 32 | 64 | 256 | 512 | 1024 | 2048;  // the default up to r08a
-constexpr int kCubesV = kCubesBase | 4096;
+// The bits by name (the numbers are what AFEM_CUBES_V, the tests, tools/ab_knobs.py
+// and profiles/ say; the kernel derives its switches from them in one block):
+constexpr int kVNoFullStores = 1;     // ablation: no value stores in the complete-layer flush
+constexpr int kVOneAdd = 2;           // ablation: one LDS add per cube
+constexpr int kVNoCubes = 4;          // ablation: no cube arithmetic
+constexpr int kVNoFullFlush = 8;      // ablation: no complete-layer flush
+constexpr int kVLoadAhead = 16;       // the next layer's coordinates loaded before the cubes
+constexpr int kVFullNT = 32;          // non-temporal value stores in the complete-layer flush
+constexpr int kVFull16B = 64;         // 16-B value stores there
+constexpr int kVOtherNT = 128;        // non-temporal value and RHS stores in the other flushes
+constexpr int kVDummyRows = 256;      // dummy rows for the corners outside the unit
+constexpr int kVCanon16B = 512;       // 16-B row stores in the canonical flush
+constexpr int kVStaged = 1024;        // the canonical path staged
+constexpr int kVSingleWriter = 2048;  // single writer
+constexpr int kVRowStride = 4096;     // scalar row bases in the complete-layer loop
+constexpr int kCubesBase = kVLoadAhead | kVFullNT | kVFull16B | kVDummyRows | kVCanon16B | kVStaged |
+                           kVSingleWriter;  // the default up to r08a
+constexpr int kCubesV = kCubesBase | kVRowStride;
 
-// register budget: 64-row planes + one coordinate layer = 17.3 KB of LDS, 9
-// waves per CU, so 2 per SIMD whatever the registers (256 VGPRs, no spill);
-// 49-row planes = 13.7 KB, 11 waves per CU: 3 per SIMD at <= 168 VGPRs
+// register budget (the compiler's figures, profiles/r11a_cubes_loop_waits.txt):
+// 64-row planes + one coordinate layer (carry) = 17 304 B of LDS, + two (no
+// carry) 19 248 B: 2 waves per SIMD whatever the registers (256 VGPRs, no
+// scratch); 49-row planes = 13 704 B with the carry, 15 648 B without: 3 per
+// SIMD at <= 168 VGPRs, which those instances reach with 136-576 B of scratch
 template <int STRIDE>
 constexpr int cube_waves() { return STRIDE == 64 ? 2 : 3; }
 template <int STRIDE, bool CARRY, bool XEX, bool YEX, bool CANON, bool HAS_RHS, bool RHS_ADD, int DIAG = kCubesV>
@@ -397,14 +442,38 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   // cube layer z; a slot of an absent neighbour (and a dummy row) holds stale
   // data, read only behind the presence mask.  Bitwise the adding instances:
   // 0.0 + x = x, and no summation order changes.
-  constexpr bool DROWS = (DIAG & 256) != 0 && STRIDE == 64;
-  constexpr bool SW = DROWS && CARRY && XEX && YEX && (DIAG & 2048) != 0 && (DIAG & 2) == 0;
+  // The switches of this instance, all derived here from its V bits (kV* above):
+  constexpr bool NO_FULL_STORES = (DIAG & kVNoFullStores) != 0, ONE_ADD = (DIAG & kVOneAdd) != 0,
+                 NO_CUBES = (DIAG & kVNoCubes) != 0, NO_FULL_FLUSH = (DIAG & kVNoFullFlush) != 0;
+  constexpr bool LOAD_AHEAD = (DIAG & kVLoadAhead) != 0, FULL_NT = (DIAG & kVFullNT) != 0,
+                 FULL_16B = (DIAG & kVFull16B) != 0, OTHER_NT = (DIAG & kVOtherNT) != 0,
+                 CANON_16B = (DIAG & kVCanon16B) != 0;
+  constexpr bool DROWS = (DIAG & kVDummyRows) != 0 && STRIDE == 64;
+  constexpr bool SW = DROWS && CARRY && XEX && YEX && (DIAG & kVSingleWriter) != 0 && !ONE_ADD;
+  constexpr bool STAGE = CANON && (DIAG & kVStaged) != 0;
+  constexpr bool RS = !CANON && (DIAG & kVRowStride) != 0;  // (with g.row_stride != 0: load_run_bases below)
   // slot o of row r of buffer b
   auto slot = [&](int b, int r, int o) -> double* {
     return SW ? &acc[b][0][0] + kAcc * r + o : &acc[b][o][r];
   };
+  // one accumulator buffer (kAcc * STRIDE doubles) filled: 16-B stores (64-row
+  // planes: the buffers are 16-B aligned), 8-B ones for the 49-row planes
+  auto clear_buffer = [&](double* buf, double fill) {
+    if constexpr ((kAcc * STRIDE) % 2 == 0) {
+      double2* const b2 = reinterpret_cast<double2*>(buf);
+#pragma unroll
+      for (int i = 0; i < (kAcc * STRIDE / 2 + 63) / 64; ++i)
+        b2[min(64 * i + lane, kAcc * STRIDE / 2 - 1)] = make_double2(fill, fill);
+    }
+    else {
+#pragma unroll
+      for (int i = 0; i < (kAcc * STRIDE + 63) / 64; ++i) buf[min(64 * i + lane, kAcc * STRIDE - 1)] = fill;
+    }
+  };
   // SW: no slot is read before its layer cycle stored to it, so there is no
   // first fill either, unless the knob asks for the NaN that shows it
+  // (both buffers in one rolled loop, not clear_buffer: the 49-row instances
+  // gain scratch with the unrolled stores here)
   if (!SW || g.acc_init != g.acc_init) {
     const double fill = SW ? g.acc_init : 0.0;
     for (int i = lane; i < 2 * kAcc * STRIDE; i += 64) (&acc[0][0][0])[i] = fill;
@@ -416,7 +485,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   const int rx = lane % kRun, ry = lane / kRun;
   const int nx = cx0 + rx, ny = cy0 + ry;
   const bool full_flush_on = g.full_flush != 0;
-  constexpr bool STAGE = CANON && (DIAG & 1024) != 0;
   int64_t pf_rb = 0, pf_re = 0, pf_r = 0;
   uint64_t pf_slot = 0;
   double pf_rhs = 0.0;
@@ -469,32 +537,42 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   // store waits for nothing the previous layer's stores are queued behind
   // (loads and stores retire in order: the wait for offsets asked for after
   // layer z - 1's stores drained those stores, a quarter of a layer later).
-  constexpr bool RS = !CANON && (DIAG & 4096) != 0;
   int64_t rs_rb = 0;
   auto load_run_bases = [&](int z) {  // clamped like prefetch_rows: no branch
     const int zz = (z >= z0 && z < z1) ? z : z0;
     rs_rb = (rows + layer_base(zz))[row_xy];
   };
-  // (sb: where the 7 x-runs' first values go, wave-uniform, V bit 4096; null: by the lanes' prefetched offsets)
-  auto flush_full = [&](int z, double* const* sb) {
-    const int b = z & 1;
+  // ---- what the flushes share.  The lane's row of buffer b: its 15 slots into
+  // v, the diagonal v[7] = -(the sum of the present neighbours' values, added
+  // in the order o = 0..14), and meas, the |det| sum the diagonal's slot held
+  auto read_row = [&](int b, uint32_t mask, double (&v)[15], double& meas) {
     const int lr = min(lane, STRIDE - 1);  // lanes past the 49 rows read a row they do not use
-    double v[15];
     double sum = 0.0;
 #pragma unroll
     for (int o = 0; o < 15; ++o) {
       v[o] = *slot(b, lr, o);
-      if (o != 7) sum += v[o];
+      if (o != 7 && ((mask >> o) & 1u)) sum += v[o];
     }
-    const double meas = v[7];
+    meas = v[7];
     v[7] = -sum;
-    if constexpr (HAS_RHS) {  // lanes without a row repeat lane 0's store
-      const bool valid = lane < kRows;
+  };
+  // the row's RHS entry from its |det| sum (RHS_ADD: onto pf_rhs); lanes
+  // without a row repeat lane 0's store (always a row)
+  auto store_rhs = [&](bool valid, double meas) {
+    if constexpr (HAS_RHS) {
       const double rv = RHS_ADD ? pf_rhs + g.f_meas * meas : g.f_meas * meas;
       const int64_t r0 = lane_i64(pf_r, 0);
       const double rv0 = lane_f64(rv, 0);
-      put<(DIAG & 128) != 0>(&rhs[valid ? pf_r : r0], valid ? rv : rv0);
+      put<OTHER_NT>(&rhs[valid ? pf_r : r0], valid ? rv : rv0);
     }
+  };
+  // (sb: where the 7 x-runs' first values go, wave-uniform, V bit 4096; null: by the lanes' prefetched offsets)
+  auto flush_full = [&](int z, double* const* sb) {
+    const int b = z & 1;
+    const int lr = min(lane, STRIDE - 1);
+    double v[15], meas;
+    read_row(b, kAllPresent, v, meas);
+    store_rhs(lane < kRows, meas);
     const int64_t rb = pf_rb;
     double* img = &acc[b][0][0];
     // (each lane storing its own row from registers instead -- 7 16-B stores at a
@@ -528,7 +606,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     // free here: the cube's sums are dead): one LDS round trip before the
     // stores instead of one per run
     double ra[kRun][2];
-    if constexpr ((DIAG & 1) == 0 && (DIAG & 64) != 0) {
+    if constexpr (!NO_FULL_STORES && FULL_16B) {
 #pragma unroll
       for (int q = 0; q < kRun; ++q) {
         ra[q][0] = img[15 * kRun * q + t2];
@@ -538,40 +616,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
 #pragma unroll
     for (int q = 0; q < kRun; ++q) {
       double* const dst = sb ? sb[q] : vals + lane_i64(rb, kRun * q);
-      if constexpr ((DIAG & 1) != 0) {
+      if constexpr (NO_FULL_STORES) {
         (void)dst;  // diagnostic: no value stores
       }
-      else if constexpr ((DIAG & 64) != 0) {
-        const double a0 = ra[q][0], a1 = ra[q][1];
-        typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
-        if constexpr ((DIAG & 32) != 0)
-          __builtin_nontemporal_store(d2u{ a0, a1 }, reinterpret_cast<d2u*>(&dst[t2]));
-        else
-          *reinterpret_cast<d2u*>(&dst[t2]) = d2u{ a0, a1 };
-      }
-      else if constexpr ((DIAG & 32) != 0) {
-        __builtin_nontemporal_store(img[15 * kRun * q + lane], &dst[lane]);
-        __builtin_nontemporal_store(img[15 * kRun * q + t1], &dst[t1]);
+      else if constexpr (FULL_16B) {
+        put2<FULL_NT>(&dst[t2], ra[q][0], ra[q][1]);
       }
       else {
-        dst[lane] = img[15 * kRun * q + lane];
-        dst[t1] = img[15 * kRun * q + t1];
+        put<FULL_NT>(&dst[lane], img[15 * kRun * q + lane]);
+        put<FULL_NT>(&dst[t1], img[15 * kRun * q + t1]);
       }
     }
     wave_lds_order();
-    if constexpr (SW) {
-      // no zero fill: the next cycle's stores overwrite every slot that is read
-    }
-    else if constexpr ((kAcc * STRIDE) % 2 == 0) {
-      double2* const img2 = reinterpret_cast<double2*>(img);
-#pragma unroll
-      for (int i = 0; i < (kAcc * STRIDE / 2 + 63) / 64; ++i)
-        img2[min(64 * i + lane, kAcc * STRIDE / 2 - 1)] = make_double2(0.0, 0.0);
-      wave_lds_order();
-    }
-    else {
-#pragma unroll
-      for (int i = 0; i < (kAcc * STRIDE + 63) / 64; ++i) img[min(64 * i + lane, kAcc * STRIDE - 1)] = 0.0;
+    if constexpr (!SW) {
+      clear_buffer(img, 0.0);
       wave_lds_order();
     }
   };
@@ -583,6 +641,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   auto flush_stage = [&](int z) {
     const int b = z & 1;
     const bool valid = lane < kRows && nx < g.npx && ny < g.npy;
+    // (presence_mask written out: through the function this instance's loop
+    // compiles to one more vector instruction)
     uint32_t mask = 0;
 #pragma unroll
     for (int o = 0; o < 15; ++o) {
@@ -592,16 +652,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
       mask |= in << o;
     }
     if (!valid) mask = 0;
-    double v[15];
-    double sum = 0.0;
-    const int lr = min(lane, STRIDE - 1);
-#pragma unroll
-    for (int o = 0; o < 15; ++o) {
-      v[o] = *slot(b, lr, o);
-      if (o != 7 && ((mask >> o) & 1u)) sum += v[o];
-    }
-    const double meas = v[7];
-    v[7] = -sum;
+    double v[15], meas;
+    read_row(b, mask, v, meas);
     wave_lds_order();  // every lane's accumulator reads before the image overwrites them
     double* img = &acc[b][0][0];
     if (lane < kRows) {  // 49 lines of 16 = 784 of the buffer's 960 doubles
@@ -611,7 +663,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
       img[16 * lane + 15] = meas;
     }
     wave_lds_order();
-    typedef double d2u __attribute__((ext_vector_type(2), aligned(16)));
     const int64_t lz = (int64_t)local_layer(g, z) * g.L + cx0;
     const bool xok = lane < 2 * 8 * kRun / 2 && cx0 + (lane >> 3) < g.npx;  // pair `lane` is line lane / 8's
     // a run past the box repeats run 0's store (always in the box), lanes
@@ -619,23 +670,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     // whatever the unit, so the waits after them count past them.  The image
     // reads of all runs first (as in flush_full).
     const int t = xok ? 2 * lane : 0;
-    d2u w[kRun];
+    d2u16 w[kRun];
 #pragma unroll
     for (int q = 0; q < kRun; ++q) {
       const int qs = cy0 + q < g.npy ? q : 0;  // uniform
-      w[q] = d2u{ img[2 * 8 * kRun * qs + t], img[2 * 8 * kRun * qs + t + 1] };
+      w[q] = d2u16{ img[2 * 8 * kRun * qs + t], img[2 * 8 * kRun * qs + t + 1] };
     }
 #pragma unroll
     for (int q = 0; q < kRun; ++q) {
       const int qs = cy0 + q < g.npy ? q : 0;
-      __builtin_nontemporal_store(w[q], reinterpret_cast<d2u*>(&cc.stage[16 * (lz + (int64_t)g.npx * (cy0 + qs)) + t]));
+      __builtin_nontemporal_store(w[q], reinterpret_cast<d2u16*>(&cc.stage[16 * (lz + (int64_t)g.npx * (cy0 + qs)) + t]));
     }
     wave_lds_order();
     if constexpr (!SW) {
-      double2* const img2 = reinterpret_cast<double2*>(img);
-#pragma unroll
-      for (int i = 0; i < (kAcc * STRIDE / 2 + 63) / 64; ++i)
-        img2[min(64 * i + lane, kAcc * STRIDE / 2 - 1)] = make_double2(0.0, 0.0);
+      clear_buffer(img, 0.0);
       wave_lds_order();
     }
   };
@@ -650,14 +698,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     const int b = z & 1;
     const bool valid = lane < kRows && nx < g.npx && ny < g.npy;
     // present neighbours and the order of their local ids: the dz groups by local layer index
-    uint32_t mask = 0;
-#pragma unroll
-    for (int o = 0; o < 15; ++o) {  // branch-free (bitwise ands of the comparisons)
-      const int xx = nx + kOffX[o], yy = ny + kOffY[o], zz = z + kOffZ[o];
-      const uint32_t in = (uint32_t)(xx >= 0) & (uint32_t)(yy >= 0) & (uint32_t)(xx < g.npx) & (uint32_t)(yy < g.npy) &
-                          (uint32_t)(zz >= 0) & (uint32_t)(zz <= g.nzc);
-      mask |= in << o;
-    }
+    uint32_t mask = presence_mask(nx, ny, z, g.npx, g.npy, g.nzc);
     if (!valid) mask = 0;
     const uint32_t gm0 = mask & 0x000Fu, gm1 = mask & 0x07F0u, gm2 = mask & 0x7800u;
     const int lm = local_layer(g, z - 1), l0 = local_layer(g, z), lp = local_layer(g, z + 1);
@@ -665,29 +706,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     const int s0 = (l0 < lm ? n1 : 0) + (lp < lm ? n2 : 0);
     const int s1 = (lm < l0 ? n0 : 0) + (lp < l0 ? n2 : 0);
     const int s2 = (lm < lp ? n0 : 0) + (l0 < lp ? n1 : 0);
-    double v[15];
-    double sum = 0.0;
-    const int lr = min(lane, STRIDE - 1);  // lanes past the 49 rows read a row they do not use
-#pragma unroll
-    for (int o = 0; o < 15; ++o) {
-      v[o] = *slot(b, lr, o);
-      if (o != 7 && ((mask >> o) & 1u)) sum += v[o];
-    }
-    const double meas = v[7];
-    v[7] = -sum;
+    double v[15], meas;
+    read_row(b, mask, v, meas);
     // the prefetched offsets are consumed without a branch (selects), so the
     // compiler keeps their load where prefetch_rows issued it
     const int64_t rb = valid ? pf_rb : 0;
     // (a 64-bit min: with only the low halves used the compiler reuses the
     // loaded high half's register at once, a write-after-write wait on the load)
     const int len = CANON ? (valid ? __popc(mask) : 0) : (valid ? (int)min(pf_re - pf_rb, (int64_t)15) : 0);
-    if constexpr (HAS_RHS) {  // lanes without a row repeat lane 0's store (always a row)
-      if constexpr (CANON && RHS_ADD) pf_rhs = rhs[pf_r];
-      const double rv = RHS_ADD ? pf_rhs + g.f_meas * meas : g.f_meas * meas;
-      const int64_t r0 = lane_i64(pf_r, 0);
-      const double rv0 = lane_f64(rv, 0);
-      put<(DIAG & 128) != 0>(&rhs[valid ? pf_r : r0], valid ? rv : rv0);
-    }
+    if constexpr (CANON && RHS_ADD) pf_rhs = rhs[pf_r];
+    store_rhs(valid, meas);
     // prefix of the row lengths within the x-run (7 lanes), the runs' offsets in the image
     int p = 0;
 #pragma unroll
@@ -723,12 +751,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
       // row's length repeat row 0's first value (always a row), so the store
       // count is fixed
       const int64_t rb0 = rbs[0];
-      if constexpr ((DIAG & 512) != 0) {
+      if constexpr (CANON_16B) {
         // 16 B per lane: pair k of row L = values j, j + 1 with j = min(2k, len - 2)
         // (the last pair overlaps the one before: same values), 8 pairs per row,
         // 7 stores per layer instead of 12; rows without values repeat row 0's
         // first pair
-        typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
 #pragma unroll
         for (int i = 0; i < (8 * kRows + 63) / 64; ++i) {
           const int Q = min(64 * i + lane, 8 * kRows - 1);
@@ -737,7 +764,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
           const bool ok = len >= 2;
           const int j = ok ? min(2 * k, len - 2) : 0;
           const int src = ok ? 15 * L + j : 0;
-          *reinterpret_cast<d2u*>(&vals[ok ? rbs[L] + j : rb0]) = d2u{ img[src], img[src + 1] };
+          *reinterpret_cast<d2u8*>(&vals[ok ? rbs[L] + j : rb0]) = d2u8{ img[src], img[src + 1] };
         }
       }
       else {
@@ -746,7 +773,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
           const int P = min(64 * i + lane, 15 * kRows - 1);
           const int L = P / 15, j = P - 15 * L;
           const bool ok = j < lens[L];
-          put<(DIAG & 128) != 0>(&vals[ok ? rbs[L] + j : rb0], img[ok ? P : 0]);
+          put<OTHER_NT>(&vals[ok ? rbs[L] + j : rb0], img[ok ? P : 0]);
         }
       }
     }
@@ -776,25 +803,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
       for (int h = 0; h < 2; ++h) {  // rl <= 7 rows x 15 = 105
         const int t = lane + 64 * h;
         const bool ok = t < rl;
-        put<(DIAG & 128) != 0>(&vals[ok ? dst + t : dst0], img[ok ? off + t : 0]);
+        put<OTHER_NT>(&vals[ok ? dst + t : dst0], img[ok ? off + t : 0]);
       }
       off += rl;
     }
     }
     wave_lds_order();
-    if constexpr (SW) {
-      // no zero fill (the image stays as stale data behind the next cycle's masks)
-    }
-    else if constexpr ((kAcc * STRIDE) % 2 == 0) {  // 16-B stores (64-row planes: buffers 16-B aligned)
-      double2* const img2 = reinterpret_cast<double2*>(img);
-#pragma unroll
-      for (int i = 0; i < (kAcc * STRIDE / 2 + 63) / 64; ++i)
-        img2[min(64 * i + lane, kAcc * STRIDE / 2 - 1)] = make_double2(0.0, 0.0);
-      wave_lds_order();
-    }
-    else {
-#pragma unroll
-      for (int i = 0; i < (kAcc * STRIDE + 63) / 64; ++i) img[min(64 * i + lane, kAcc * STRIDE - 1)] = 0.0;
+    if constexpr (!SW) {
+      clear_buffer(img, 0.0);
       wave_lds_order();
     }
   };
@@ -933,7 +949,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
       for (int b = 0; b < 8; ++b) ev[a][b] = 0.0;
     }
 #pragma unroll
-    for (int t = 0; t < ((DIAG & 4) ? 0 : 6); ++t) {
+    for (int t = 0; t < (NO_CUBES ? 0 : 6); ++t) {
       const int v1 = tet_v(t, 1), v2 = tet_v(t, 2);
       const P3 e1 = psub(X[v1], X[0]), e2 = psub(X[v2], X[0]), e3 = psub(X[7], X[0]);
       P3 k[4];
@@ -1019,7 +1035,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
         if (is_edge(a, b) && !(CARRY && cbit(a, 2) && cbit(b, 2)) &&
             !(XEX && !cbit(a, 0) && !cbit(b, 0) && !(cbit(a, 2) && cbit(b, 2))) &&
             !(YEX && !cbit(a, 1) && !cbit(b, 1) && !(cbit(a, 2) && cbit(b, 2)))) {
-          if constexpr (DIAG & 2) {
+          if constexpr (ONE_ADD) {
             dsum += ev[a][b];
           }
           else if constexpr (DROWS) {
@@ -1034,14 +1050,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
 #pragma unroll
     for (int c = 0; c < 8; ++c)
       if (!(CARRY && cbit(c, 2)) && !(XEX && !cbit(c, 0) && !cbit(c, 2)) && !(YEX && !cbit(c, 1) && !cbit(c, 2))) {
-        if constexpr (DIAG & 2)
+        if constexpr (ONE_ADD)
           dsum += mv[c];
         else if constexpr (DROWS)
           sum_d(slot_d(bb_, bt_, c, 7), mv[c]);  // |det| sums
         else
           atomicAdd(base_at(inm, bb_, bt_, c) + STRIDE * 7, kept(c, mv[c]));  // |det| sums
       }
-    if constexpr ((DIAG & 2) != 0) atomicAdd(&acc[bb_][0][rs], dsum);
+    if constexpr (ONE_ADD) atomicAdd(&acc[bb_][0][rs], dsum);
   };
 
   // ---- walk the cube layers upwards (coordinates staged one layer ahead)
@@ -1122,10 +1138,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
     // node layer z0 - 1's buffer took real sums: clear it for node layer z0 + 1
     // (SW: not needed, node layer z0 + 1's cycle stores to every slot it reads)
     if constexpr (DROWS && !SW) {
-      double2* const b2 = reinterpret_cast<double2*>(&acc[zc & 1][0][0]);
-#pragma unroll
-      for (int i = 0; i < (kAcc * STRIDE / 2 + 63) / 64; ++i)
-        b2[min(64 * i + lane, kAcc * STRIDE / 2 - 1)] = make_double2(0.0, 0.0);
+      clear_buffer(&acc[zc & 1][0][0], 0.0);
       wave_lds_order();
     }
     store_layer(zc & 1);
@@ -1139,10 +1152,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
   // the cubes, the flush, the staging.
   auto layer_step = [&](int zc, auto&& fl) {
     prefetch_rows(zc);
-    if constexpr ((DIAG & 16) != 0) next_layer(zc + 2);
+    if constexpr (LOAD_AHEAD) next_layer(zc + 2);
     wave_lds_order();
     cubes(zc);
-    if constexpr ((DIAG & 16) == 0) next_layer(zc + 2);
+    if constexpr (!LOAD_AHEAD) next_layer(zc + 2);
     wave_lds_order();
     fl(zc);
     store_layer(zc & 1);
@@ -1165,12 +1178,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
             for (; zc < zf1; ++zc) {
               pf_r = layer_base(zc) + row_xy;  // zf0 <= zc < zf1: inside the segment
               if constexpr (RHS_ADD) pf_rhs = rhs[pf_r];
-              if constexpr ((DIAG & 16) != 0) next_layer(zc + 2);
+              if constexpr (LOAD_AHEAD) next_layer(zc + 2);
               wave_lds_order();
               cubes(zc);
-              if constexpr ((DIAG & 16) == 0) next_layer(zc + 2);
+              if constexpr (!LOAD_AHEAD) next_layer(zc + 2);
               wave_lds_order();
-              if constexpr (!(DIAG & 8)) flush_full(zc, run_base);
+              if constexpr (!NO_FULL_FLUSH) flush_full(zc, run_base);
               store_layer(zc & 1);
 #pragma unroll
               for (int q = 0; q < kRun; ++q) run_base[q] += g.row_stride;
@@ -1180,7 +1193,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(cube_waves<S
 #pragma nounroll
         for (; zc < zf1; ++zc)
           layer_step(zc, [&](int z) {
-            if constexpr (!(DIAG & 8)) flush_full(z, nullptr);
+            if constexpr (!NO_FULL_FLUSH) flush_full(z, nullptr);
           });
       }
     }
@@ -1210,11 +1223,7 @@ __global__ void k_cube_stage_maps(int64_t n, int npx, int npy, int nzc, const in
   const int z = (int)(i / L);
   const int64_t rem = i - (int64_t)z * L;
   const int y = (int)(rem / npx), x = (int)(rem - (int64_t)y * npx);
-  uint32_t mask = 0;
-  for (int o = 0; o < 15; ++o) {
-    const int xx = x + kOffX[o], yy = y + kOffY[o], zz = z + kOffZ[o];
-    if (xx >= 0 && yy >= 0 && xx < npx && yy < npy && zz >= 0 && zz <= nzc) mask |= 1u << o;
-  }
+  const uint32_t mask = presence_mask(x, y, z, npx, npy, nzc);
   const uint64_t sl = slot[i];
   uint64_t w = 0;
   for (int o = 0; o < 15; ++o)
@@ -1378,26 +1387,47 @@ constexpr double kCostGeneral = 1.67;
 constexpr double kCostTop = 0.90;
 constexpr int kXcds = 8;
 
-// what the kernel's walk runs on the unit (the kernel's own zc_first, zc_last, full_range)
+// One unit's walk, for the unit with first row (cx0, cy0) over the owned node
+// layers [z0, z1): cube layers zc_first..zc_last, the complete node layers
+// [zf0, zf1) (flush_full; none: zf0 = zf1 = zc_last + 1), below: it starts with
+// the cube layer under the segment, top: it ends with the box's top node layer.
+// The kernel does NOT call this: it keeps the same arithmetic in place (its
+// zc_first, zc_last, xy_full, full_range, and the conditions of the layer below
+// and of the top layer), because taking the walk from here, as a struct or as
+// scalars, at the kernel's top or where the z walk starts, spilled 6 to 16 more
+// scalar registers in 28 or more of the instances.  A
+// change to either side has to be made on the other.
+struct CubeWalk {
+  int zc_first, zc_last, zf0, zf1;
+  bool below, top;
+};
+__host__ __device__ __forceinline__ CubeWalk cube_walk(const CubeGeom& g, bool canon, int cx0, int cy0, int z0, int z1)
+{
+  CubeWalk w;
+  w.zc_first = std::max(z0 - 1, 0);
+  w.zc_last = std::min(z1 - 1, g.nzc - 1);
+  const int zhi = w.zc_last + 1;
+  const bool xy_full = cx0 >= 1 && cx0 + kRun <= g.npx - 1 && cy0 >= 1 && cy0 + kRun <= g.npy - 1;
+  const bool on = !canon && xy_full && g.full_flush != 0;
+  w.zf0 = on ? std::min(std::max(z0, g.k0 + 1), zhi) : zhi;
+  w.zf1 = on ? std::max(std::min(zhi, g.nzc), w.zf0) : zhi;
+  w.below = w.zc_first < z0;
+  w.top = zhi >= z0 && zhi < z1;
+  return w;
+}
+// what the walk runs on the unit: counted from cube_walk and nothing else
 struct CubeUnitWork {
   int below, full, general, top;
 };
 CubeUnitWork cube_unit_work(const CubeGeom& g, bool canon, const CubeUnit& u)
 {
-  const int cx0 = kRun * u.cx, cy0 = kRun * u.cy;
-  const int zc_first = std::max(u.z0 - 1, 0), zc_last = std::min(u.z1 - 1, g.nzc - 1);
-  const bool xy_full = cx0 >= 1 && cx0 + kRun <= g.npx - 1 && cy0 >= 1 && cy0 + kRun <= g.npy - 1;
-  const int zhi = zc_last + 1;
-  int zf0 = zhi, zf1 = zhi;
-  if (!canon && xy_full && g.full_flush) {
-    zf0 = std::min(std::max(u.z0, g.k0 + 1), zhi);
-    zf1 = std::max(std::min(zhi, g.nzc), zf0);
-  }
+  const CubeWalk k = cube_walk(g, canon, kRun * u.cx, kRun * u.cy, u.z0, u.z1);
   CubeUnitWork w;
-  w.below = zc_first < u.z0 ? 1 : 0;
-  w.full = zf1 - zf0;
-  w.general = std::max(zhi - u.z0, 0) - w.full;
-  w.top = (zhi >= u.z0 && zhi < u.z1) ? 1 : 0;
+  w.below = k.below ? 1 : 0;
+  w.full = k.zf1 - k.zf0;
+  // every cube layer after the one below flushes one node layer: the range's complete, the rest general
+  w.general = std::max(k.zc_last + 1 - (k.zc_first + w.below), 0) - w.full;
+  w.top = k.top ? 1 : 0;
   return w;
 }
 double cube_unit_cost(const CubeGeom& g, bool canon, const CubeUnit& u)
@@ -1495,6 +1525,83 @@ void build_cube_units(const Mesh& m, Structure& S, const CubeGeom& g, bool canon
   std::copy(key, key + 12, S.cube_units_key);
 }
 
+// ---- the compiled instances: {stride, carry, xex, yex, canon, V} and the
+// kernel of each RHS mode it is compiled in (null: not compiled in that one)
+enum { kRhsNone = 0, kRhsSet = 1, kRhsAdd = 2 };
+constexpr int kInNone = 1 << kRhsNone, kInSet = 1 << kRhsSet, kInAll = kInNone | kInSet | 1 << kRhsAdd;
+using CubeKernel = decltype(&k_assemble_cubes<64, true, true, true, false, true, false>);
+struct CubeInstance {
+  int stride;
+  bool carry, xex, yex, canon;
+  int v;
+  CubeKernel k[3];
+};
+template <int STRIDE, bool CARRY, bool XEX, bool YEX, bool CANON, int V, int MODES>
+CubeInstance cube_instance()
+{
+  CubeInstance i{ STRIDE, CARRY, XEX, YEX, CANON, V, { nullptr, nullptr, nullptr } };
+  if constexpr ((MODES & kInNone) != 0) i.k[kRhsNone] = &k_assemble_cubes<STRIDE, CARRY, XEX, YEX, CANON, false, false, V>;
+  if constexpr ((MODES & kInSet) != 0) i.k[kRhsSet] = &k_assemble_cubes<STRIDE, CARRY, XEX, YEX, CANON, true, false, V>;
+  if constexpr ((MODES & 1 << kRhsAdd) != 0) i.k[kRhsAdd] = &k_assemble_cubes<STRIDE, CARRY, XEX, YEX, CANON, true, true, V>;
+  return i;
+}
+// the other values AFEM_CUBES_V can take, RHS set only: the headline instance (box
+// and natural lattices: 64 rows, carry, both exchanges) with V, and the canonical
+// single-pass one with its counterpart, which never carries bits 1024 and 4096
+template <int... V>
+void add_variants(std::vector<CubeInstance>& t)
+{
+  (t.push_back(cube_instance<64, true, true, true, false, V, kInSet>()), ...);
+  (t.push_back(cube_instance<64, true, true, true, true, V & ~(kVStaged | kVRowStride), kInSet>()), ...);
+}
+constexpr int kCanonV = kCubesBase & ~kVStaged;
+std::vector<CubeInstance> cube_instances()
+{
+  constexpr int kB = kCubesBase;
+  std::vector<CubeInstance> t{
+    // what AFEM_CUBES_STRIDE / _CARRY / _XEX / _YEX and bit 4096 of AFEM_CUBES_V select, in every RHS mode
+    cube_instance<64, true, true, true, false, kCubesV, kInAll>(),
+    cube_instance<64, true, true, true, false, kB, kInAll>(),
+    cube_instance<64, true, true, true, true, kCanonV, kInAll>(),
+    cube_instance<49, true, true, true, false, kB, kInAll>(),
+    cube_instance<64, true, true, false, false, kB, kInAll>(),
+    cube_instance<64, true, false, false, false, kB, kInAll>(),
+    cube_instance<49, false, false, false, false, kB, kInAll>(),
+    cube_instance<64, false, false, false, false, kB, kInAll>(),
+    // the staged canonical instances (V with bit 1024): no RHS, k_cube_unstage writes it
+    cube_instance<64, true, true, true, true, kB, kInNone>(),
+    cube_instance<64, true, true, true, true, kB | kVNoFullStores, kInNone>(),
+    cube_instance<64, true, true, true, true, kB | kVNoCubes, kInNone>(),
+    cube_instance<64, true, true, true, true, kB & ~kVSingleWriter, kInNone>(),
+  };
+  add_variants<0, kVLoadAhead | kVFullNT | kVFull16B, kB | kVNoFullStores, kB | kVOneAdd, kB | kVNoCubes,
+               kB | kVNoFullFlush, kB & ~kVFullNT, kB & ~kVCanon16B, kB & ~kVStaged, kB & ~kVSingleWriter,
+               kB & ~(kVStaged | kVSingleWriter), kCubesV | kVNoFullStores, kCubesV | kVNoCubes,
+               kCubesV | kVNoFullFlush>(t);
+  return t;
+}
+const std::vector<CubeInstance> kCubeInstances = cube_instances();
+// the instance's kernel for the RHS mode; null: not compiled
+CubeKernel find_cube_kernel(int stride, bool carry, bool xex, bool yex, bool canon, int v, int mode)
+{
+  for (const CubeInstance& i : kCubeInstances)
+    if (i.stride == stride && i.carry == carry && i.xex == xex && i.yex == yex && i.canon == canon && i.v == v && i.k[mode])
+      return i.k[mode];
+  return nullptr;
+}
+// k_cube_unstage by AFEM_UNSTAGE_V, RHS set only (the other RHS modes: UV 3, the default)
+using UnstageKernel = decltype(&k_cube_unstage<true, false>);
+const UnstageKernel kUnstageSet[4] = { &k_cube_unstage<true, false, 0>, &k_cube_unstage<true, false, 1>,
+                                       &k_cube_unstage<true, false, 2>, &k_cube_unstage<true, false, 3> };
+
+// a knob that holds an integer (not set: dflt), and "the knob is set to 0"
+int knob_int(const char* name, int dflt)
+{
+  const char* e = variant(name);
+  return e ? atoi(e) : dflt;
+}
+bool knob_off(const char* name) { return knob_int(name, 1) == 0; }
+
 }  // namespace
 
 // Structure::cube_row_stride, once per structure (build_structure).  The node
@@ -1539,8 +1646,7 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
 {
   const Mesh& m = *b.mesh;
   Structure& S = b.s;
-  const char* ce = variant("AFEM_ASSEMBLY_CUBES");  // 0: the strip / stencil kernels
-  if (ce && atoi(ce) == 0) return false;
+  if (knob_off("AFEM_ASSEMBLY_CUBES")) return false;  // the strip / stencil kernels
   CubeGeom g{};
   bool canon = false;
   if (!cube_lattice_geom(m, S, b.nb_dof, g, canon)) return false;
@@ -1559,68 +1665,44 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
   g.ns = 0;
   g.s_coef = coef / 6.0;
   g.f_meas = f / 24.0;
-  const char* fe = variant("AFEM_CUBES_FULL");
-  g.full_flush = (fe && atoi(fe) == 0) ? 0 : 1;
+  g.full_flush = knob_off("AFEM_CUBES_FULL") ? 0 : 1;
   // the single-writer instances' first accumulator fill (a test's knob: with a NaN
   // there the outputs stay finite only if no flush reads a slot its layer did not write)
   const char* ie = variant("AFEM_CUBES_ACC_INIT");
   g.acc_init = (ie && (ie[0] == 'n' || ie[0] == 'N')) ? std::numeric_limits<double>::quiet_NaN() : 0.0;
   // the unit table (built once per structure and plan): AFEM_CUBES_SCHED=0 keeps the
   // lattice order and the equal-count eighths, for the A/B of the order alone
-  const char* sce = variant("AFEM_CUBES_SCHED");
-  const char* be = variant("AFEM_CUBES_BAND");
-  build_cube_units(m, S, g, canon, (sce && atoi(sce) == 0) ? 0 : 1, be ? std::max(0, atoi(be)) : 0, pat);
+  build_cube_units(m, S, g, canon, knob_off("AFEM_CUBES_SCHED") ? 0 : 1, std::max(0, knob_int("AFEM_CUBES_BAND", 0)),
+                   pat);
   g.units = reinterpret_cast<const uint2*>(S.cube_units.p);
-  // accumulator planes of 64 rows (19.3 KB of LDS, 8 waves per CU), or of 49
-  // (AFEM_CUBES_STRIDE=49: 15.6 KB, 10 waves -- with the carry it spills: r04y)
-  const char* se = variant("AFEM_CUBES_STRIDE");
-  const bool s49 = se && atoi(se) == 49;
+  // ---- the instance wanted, then looked up in kCubeInstances.
+  // Accumulator planes of 64 rows, or of 49 (AFEM_CUBES_STRIDE=49; LDS and
+  // occupancy: cube_waves -- with the carry it spills: r04y)
+  const bool s49 = knob_int("AFEM_CUBES_STRIDE", 64) == 49;
   // the top face's sums carried in registers to the next cube layer (AFEM_CUBES_CARRY=0: not;
   // r04y C2: 0.605 ms with the carry at 64-row planes, 0.660 without at 49); the x = 1 face's
-  // shared with lane + 1 over DPP (AFEM_CUBES_XEX=0: not; needs the carry)
-  const char* ke = variant("AFEM_CUBES_CARRY");
-  const bool carry = canon || !(ke && atoi(ke) == 0);
-  const char* xe = variant("AFEM_CUBES_XEX");
-  const bool xex = canon || (carry && !(xe && atoi(xe) == 0));
-  // and the y = 1 face's with lane + 8 (AFEM_CUBES_YEX=0: not; needs the x exchange)
-  const char* ye = variant("AFEM_CUBES_YEX");
-  const bool yex = canon || (xex && !(ye && atoi(ye) == 0));
-#define AFEM_CUBES_K(S, C, X, Y, N, D)                                                                               \
-  (rhs ? (rhs_add ? &k_assemble_cubes<S, C, X, Y, N, true, true, D> : &k_assemble_cubes<S, C, X, Y, N, true, false, D>) \
-       : &k_assemble_cubes<S, C, X, Y, N, false, false, D>)
-  const char* de = variant("AFEM_CUBES_V");
-  const int diag = de ? atoi(de) : kCubesV;
-  // canonical structures: the staged instance (below), or the single-pass one (V without 1024).
-  // The headline instance (64 rows, carry, both exchanges) takes the default V, or the
-  // same with or without bit 4096 as AFEM_CUBES_V says (every RHS mode); the canonical
-  // ones and the box instances without an exchange or with 49-row planes stay at the V
-  // they were built with (no bit 4096)
-  constexpr int kB = kCubesBase;
-  auto* kern = canon ? AFEM_CUBES_K(64, true, true, true, true, kB & ~1024)
-               : carry ? (xex ? (yex ? (s49 ? AFEM_CUBES_K(49, true, true, true, false, kB)
-                                            : ((diag & 4096) ? AFEM_CUBES_K(64, true, true, true, false, kB | 4096)
-                                                             : AFEM_CUBES_K(64, true, true, true, false, kB)))
-                                     : AFEM_CUBES_K(64, true, true, false, false, kB))
-                              : AFEM_CUBES_K(64, true, false, false, false, kB))
-                       : (s49 ? AFEM_CUBES_K(49, false, false, false, false, kB)
-                              : AFEM_CUBES_K(64, false, false, false, false, kB));
-#undef AFEM_CUBES_K
+  // shared with lane + 1 over DPP (AFEM_CUBES_XEX=0: not; needs the carry); and the y = 1
+  // face's with lane + 8 (AFEM_CUBES_YEX=0: not; needs the x exchange).  Canonical
+  // structures: always all three.
+  const bool carry = canon || !knob_off("AFEM_CUBES_CARRY");
+  const bool xex = canon || (carry && !knob_off("AFEM_CUBES_XEX"));
+  const bool yex = canon || (xex && !knob_off("AFEM_CUBES_YEX"));
+  const bool all3 = carry && xex && yex;
+  const int diag = knob_int("AFEM_CUBES_V", kCubesV);
+  int mode = rhs ? (rhs_add ? kRhsAdd : kRhsSet) : kRhsNone;
+  // 49-row planes exist with all three or with none of them.  The headline instance
+  // (box, 64 rows, all three) takes bit 4096 as AFEM_CUBES_V says, in every RHS mode;
+  // every other instance stays at the V it was built with: the canonical single-pass
+  // one at the base without 1024, the rest at the base
+  int stride = !canon && s49 && (all3 || !carry) ? 49 : 64;
+  int v = canon ? kCanonV : (all3 && !s49 && (diag & kVRowStride) != 0) ? kCubesV : kCubesBase;
   // AFEM_CUBES_V: another variant of the headline instance (generator boxes and
-  // natural lattices, RHS set) or of the canonical one (RHS set)
-  if (diag != (kB | 4096) && diag != kB && carry && xex && yex && rhs && !rhs_add) {
-    switch (diag) {
-#define AFEM_CUBES_D(D)                                                                                              \
-  case D:                                                                                                            \
-    kern = canon ? &k_assemble_cubes<64, true, true, true, true, true, false, (D) & ~(1024 | 4096)>                 \
-                 : &k_assemble_cubes<64, true, true, true, false, true, false, D>;                                  \
-    break;
-      AFEM_CUBES_D(0) AFEM_CUBES_D(112) AFEM_CUBES_D(kB | 1) AFEM_CUBES_D(kB | 4)
-      AFEM_CUBES_D(kB | 8) AFEM_CUBES_D(kB | 2) AFEM_CUBES_D(kB & ~512) AFEM_CUBES_D(kB & ~1024)
-      AFEM_CUBES_D(kB & ~32) AFEM_CUBES_D(kB & ~2048) AFEM_CUBES_D(kB & ~(1024 | 2048))
-      AFEM_CUBES_D(kB | 4096 | 1) AFEM_CUBES_D(kB | 4096 | 4) AFEM_CUBES_D(kB | 4096 | 8)
-#undef AFEM_CUBES_D
-      default: break;
-    }
+  // natural lattices) or of the canonical one, RHS set only; a value that is not
+  // in the list leaves the default
+  if (diag != kCubesV && diag != kCubesBase && all3 && mode == kRhsSet &&
+      find_cube_kernel(64, true, true, true, false, diag, kRhsSet)) {
+    stride = 64;
+    v = canon ? diag & ~(kVStaged | kVRowStride) : diag;
   }
   CubeCanon cc{ canon ? S.cube_phys.p : nullptr, canon ? S.cube_rb.p : nullptr, canon ? S.cube_slot.p : nullptr,
                 nullptr };
@@ -1628,7 +1710,7 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
   // lines (no row maps, no RHS), k_cube_unstage moves them into the caller's rows
   // (every lattice node one of this structure's rows, as canonical_lattice builds it)
   const int64_t n_lat = g.L * (int64_t)(g.nzc + 1);
-  const bool staged = canon && (diag & 1024) != 0 && n_lat == S.n_rows;
+  const bool staged = canon && (diag & kVStaged) != 0 && n_lat == S.n_rows;
   if (staged) {
     if (S.cube_lat.n != (size_t)n_lat) {
       S.cube_lat.alloc(n_lat);
@@ -1639,31 +1721,20 @@ bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add)
     }
     if (b.cube_stage.n != (size_t)(16 * n_lat)) b.cube_stage.alloc(16 * n_lat);
     cc.stage = b.cube_stage.p;
-    kern = &k_assemble_cubes<64, true, true, true, true, false, false, kCubesBase | 1024>;
-    if (diag != (kCubesBase | 4096) && diag != kCubesBase) {
-      switch (diag) {
-#define AFEM_CUBES_S(D)                                                                                              \
-  case D:                                                                                                            \
-    kern = &k_assemble_cubes<64, true, true, true, true, false, false, D>;                                          \
-    break;
-        AFEM_CUBES_S(kCubesBase | 1024 | 1) AFEM_CUBES_S(kCubesBase | 1024 | 4) AFEM_CUBES_S(kCubesBase & ~2048)
-#undef AFEM_CUBES_S
-        default: break;
-      }
-    }
+    // the staged instance exists without RHS only, in the default V or the listed ones
+    mode = kRhsNone;
+    v = find_cube_kernel(64, true, true, true, true, diag, kRhsNone) ? diag : kCubesBase;
   }
+  const CubeKernel kern = find_cube_kernel(stride, carry, xex, yex, canon, v, mode);
+  AFEM_REQUIRE(kern != nullptr, AFEM_ERR_NOT_IMPL, "cube kernel: no such instance");
   hipLaunchKernelGGL(kern, dim3((unsigned)S.cube_units_n), dim3(64), 0, ctx.stream, g, S.row_ptr.p, m.coords.p,
                      b.values.p, rhs, cc);
   AFEM_LAUNCHED();
   if (staged) {
     const int64_t n = S.n_rows;
-    auto* un = rhs ? (rhs_add ? &k_cube_unstage<true, true> : &k_cube_unstage<true, false>)
-                   : &k_cube_unstage<false, false>;
-    const char* uve = variant("AFEM_UNSTAGE_V");
-    const int uv = uve ? atoi(uve) : 3;
-    if (rhs && !rhs_add && uv == 0) un = &k_cube_unstage<true, false, 0>;
-    if (rhs && !rhs_add && uv == 1) un = &k_cube_unstage<true, false, 1>;
-    if (rhs && !rhs_add && uv == 2) un = &k_cube_unstage<true, false, 2>;
+    const int uv = knob_int("AFEM_UNSTAGE_V", 3);
+    UnstageKernel un = rhs ? (rhs_add ? &k_cube_unstage<true, true> : kUnstageSet[3]) : &k_cube_unstage<false, false>;
+    if (rhs && !rhs_add && uv >= 0 && uv < 3) un = kUnstageSet[uv];
     hipLaunchKernelGGL(un, dim3((unsigned)grid_for(n, 64)), dim3(64), 0, ctx.stream, n, S.row_ptr.p, S.cube_lat.p,
                        S.cube_pinv.p, b.cube_stage.p, g.f_meas, b.values.p, rhs);
     AFEM_LAUNCHED();

@@ -20,7 +20,10 @@ start the range next to the ghost layer below.  A random-numbered lattice
 
 Gates as in test_gpu_cubes_single_writer.py: the structure bit-exact, values
 and RHS within 1e-12 of the oracle's largest entry, everything between two
-cube runs bitwise."""
+cube runs bitwise.
+
+test_dispatch_fallback pins what assemble_cubes runs when AFEM_CUBES_V names
+no compiled instance of the wanted family and RHS mode: the default one."""
 import numpy as np
 import pytest
 
@@ -177,5 +180,68 @@ def test_row_stride_array_lattices(ctx, variant, numbering):
         _same(on, box, "natural lattice against the generator box")
     else:
         assert np.array_equal(on[1][p], box[1]), "RHS is not the generator box's, permuted"
+    m1.close()
+    m0.close()
+
+
+V_UNLISTED = 12345  # a value cubes.hip compiles no instance for
+V_SET_ONLY = V_ON | 8  # compiled with RHS set only (an ablation: no complete-layer flush, wrong values if it ran)
+
+
+def _values_only(bsr):
+    """One cube run without an RHS: the values."""
+    bsr.resetMatrixValues()
+    bsr.assemblePoissonP1(1.0, F)
+    assert bsr.stats()["last_kernel"] == KERNEL_CUBES
+    return bsr.download()[2]
+
+
+def _check_fallback(variant, bsr, ls, what):
+    """AFEM_CUBES_V with a value no instance is compiled for (every RHS mode), or
+    with one compiled for RHS set only (RHS add, no RHS): the default instance of
+    the family runs, values and RHS bitwise the default's."""
+    def run(v, mode):
+        """The run under test with AFEM_CUBES_V = v; an add run goes onto the
+        default's set run (V_SET_ONLY itself runs under RHS set)."""
+        variant("AFEM_CUBES_V", None)
+        bsr.resetMatrixValues()
+        if mode == "add":
+            bsr.assemblePoissonP1(1.0, F, ls.rhsVariable(), rhs_mode="set")
+            bsr.resetMatrixValues()
+        variant("AFEM_CUBES_V", v)
+        bsr.assemblePoissonP1(1.0, F, ls.rhsVariable(), rhs_mode=mode)
+        assert bsr.stats()["last_kernel"] == KERNEL_CUBES
+        return bsr.download()[2], ls.rhs_host()
+
+    ref = {"set": run(None, "set"), "add": run(None, "add")}
+    ref_values = _values_only(bsr)
+    assert np.isfinite(ref_values).all() and np.array_equal(ref_values, ref["set"][0])
+    assert np.array_equal(ref["add"][1], ref["set"][1] + ref["set"][1])
+    for v, modes in ((V_UNLISTED, ("set", "add")), (V_SET_ONLY, ("add",))):
+        for mode in modes:
+            _same(run(str(v), mode), ref[mode], f"{what}: V={v} {mode}")
+        assert np.array_equal(_values_only(bsr), ref_values), f"{what}: V={v} no RHS: values differ"
+    variant("AFEM_CUBES_V", None)
+
+
+def test_dispatch_fallback(ctx, variant):
+    """n = 16, nz = 5, segments of 3 layers: three columns of units per axis, the
+    middle one complete, the outer ones on the box's faces with a partial
+    column, two segments.  The generator box (the headline instance), then the
+    same box as arrays in a random numbering (the canonical and staged ones)."""
+    variant("AFEM_CUBES_ZS", "3")
+    m0 = af.Mesh.structured(ctx, 3, 16, 5, jitter=0.2, seed=17)
+    b0, l0 = _system(ctx, m0)
+    _check_fallback(variant, b0, l0, "box")
+    cells, coords, _ = m0.download()
+    rng = np.random.default_rng(17)
+    p = rng.permutation(coords.shape[0])
+    pc = np.empty_like(coords)
+    pc[p] = coords
+    cells = np.ascontiguousarray(p[cells].astype(np.int32)[rng.permutation(cells.shape[0])])
+    m1 = af.Mesh.from_arrays(ctx, 3, cells, pc)
+    b1, l1 = _system(ctx, m1)
+    assert b1.stats()["cube_lattice"] == 3, b1.stats()
+    _check_fallback(variant, b1, l1, "random-numbered arrays")
     m1.close()
     m0.close()
