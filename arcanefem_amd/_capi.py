@@ -23,6 +23,9 @@ AFEM_SOLVER_DIRECT = 2
 AFEM_NEUMANN_VALUE = 0
 AFEM_NEUMANN_NORMAL = 1
 AFEM_NEUMANN_TRACTION = 2
+AFEM_DIRICHLET_PENALTY = 0
+AFEM_DIRICHLET_ROW_ELIMINATION = 1
+AFEM_DIRICHLET_ROW_COLUMN_ELIMINATION = 2
 UNIQUE_ID_BYTES = 128
 ERRORS = {1: "ArgumentException", 2: "HipError", 3: "NotImplementedException", 4: "StateError",
           5: "NotFound", 6: "CommError", 7: "LimitExceeded"}
@@ -208,6 +211,8 @@ SIGNATURES = {
     "afem_ls_elimination_value": [P, PP],
     "afem_ls_dirichlet_penalty": [P, P, I64, D, D, INT],
     "afem_ls_dirichlet_row_elimination": [P, P, I64, D, INT],
+    "afem_ls_dirichlet_row_column_elimination": [P, P, I64, D, INT],
+    "afem_ls_dirichlet_vectorial": [P, INT, P, I64, P, ctypes.c_uint, INT, D, INT],
     "afem_ls_apply_boundary_conditions": [P],
     "afem_ls_clear_values": [P],
     "afem_ls_solve": [P, ctypes.POINTER(SolveStats)],

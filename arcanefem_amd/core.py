@@ -262,11 +262,14 @@ class BSRFormat:
 
     def assembleElasticityP1Ex(self, lam: float, mu2: float, mass_coef: float = 0.0, body_force=None,
                                rhs_dptr: int | None = None, rhs_mode: str = "add"):
-        """Block-3 tetrahedra: lambda/mu2 stiffness + mass_coef * consistent mass
-        (Newmark LHS c0 M + K) and, with body_force (3 floats), the vectorial
-        constant source into rhs_dptr (3 per owned node; rhs_mode as above)."""
+        """Block-3 tetrahedra or block-2 triangles: lambda/mu2 stiffness +
+        mass_coef * consistent mass (Newmark LHS c0 M + K) and, with body_force
+        (NB_DOF floats), the vectorial constant source into rhs_dptr (NB_DOF
+        per owned node; rhs_mode as above)."""
         f = None
         if body_force is not None:
+            if len(body_force) != self.nb_dof:
+                raise ValueError(f"body_force needs {self.nb_dof} components")
             f = (ctypes.c_double * 3)(*[float(x) for x in body_force])
         call("afem_bsr_assemble_elasticity_p1_ex", self.h, lam, mu2, mass_coef, f,
              ctypes.c_void_p(rhs_dptr) if rhs_dptr else None, _rhs_mode(rhs_mode))
@@ -459,6 +462,30 @@ class DoFLinearSystem:
         self._check_init()
         dofs = np.ascontiguousarray(dofs, dtype=np.int32)
         call("afem_ls_dirichlet_row_elimination", self.impl, _ptr(dofs), dofs.shape[0], value, C.AFEM_MEM_HOST)
+
+    def applyDirichletViaRowColumnElimination(self, dofs, value: float):
+        """eliminateRowColumn for a list of DoFs (one rank, owned columns)."""
+        self._check_init()
+        dofs = np.ascontiguousarray(dofs, dtype=np.int32)
+        call("afem_ls_dirichlet_row_column_elimination", self.impl, _ptr(dofs), dofs.shape[0], value,
+             C.AFEM_MEM_HOST)
+
+    DIRICHLET_METHODS = {"penalty": C.AFEM_DIRICHLET_PENALTY, "row-elimination": C.AFEM_DIRICHLET_ROW_ELIMINATION,
+                         "row-column-elimination": C.AFEM_DIRICHLET_ROW_COLUMN_ELIMINATION}
+
+    def applyDirichletVectorial(self, nodes, u, method: str = "penalty", penalty: float = 1.0e30):
+        """Gpu::BoundaryConditions::apply{,Point}DirichletVia...Vectorial: `u`
+        has one entry per component of a node (NB_DOF = len(u)), None for the
+        reference's NULL (component left free); `nodes` are the nodes of the
+        face group or of the point group; method "penalty", "row-elimination"
+        or "row-column-elimination"."""
+        self._check_init()
+        nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+        k = len(u)
+        mask = sum(1 << i for i, x in enumerate(u) if x is not None)
+        vals = (ctypes.c_double * 3)(*[0.0 if x is None else float(x) for x in u])
+        call("afem_ls_dirichlet_vectorial", self.impl, k, _ptr(nodes), nodes.shape[0], vals, mask,
+             self.DIRICHLET_METHODS[method], penalty, C.AFEM_MEM_HOST)
 
     def applyBoundaryConditions(self):
         call("afem_ls_apply_boundary_conditions", self.impl)

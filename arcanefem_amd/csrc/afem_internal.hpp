@@ -472,6 +472,9 @@ struct LinearSystem {
   // host COO (Aleph semantics)
   std::map<std::pair<int32_t, int32_t>, double> add_map, set_map;
   std::map<int32_t, std::pair<uint8_t, double>> host_elim;
+  // a device list flagged row+column eliminations (ls_set_list kind 2,
+  // ls_set_vectorial): ls_apply_bcs runs the column pass; cleared with host_elim
+  bool list_elim_rc = false;
   // solver work
   DevBuf<double> r, z, p, q, dinv, partial, scal;
   mutable DevBuf<uint8_t> pat_flag;  // rows whose columns follow the dominant offset pattern (pattern SpMV)
@@ -526,7 +529,9 @@ void assemble_scalar(Bsr& b, double coef, double f, double* rhs, int rhs_add);
 // the cell-first cube kernel on generator boxes / slabs (cubes.hip); false: not applicable
 bool assemble_cubes(Bsr& b, double coef, double f, double* rhs, int rhs_add);
 void cube_row_stride(const Mesh& m, Structure& s, int nb_dof);  // sets s.cube_row_stride (structure build)
-void assemble_elasticity_tri(Bsr& b, double lambda, double mu2);
+// block-2 triangles: + mass_coef x consistent mass, body force f[2] into rhs (2 per owned node) when f is given
+void assemble_elasticity_tri(Bsr& b, double lambda, double mu2, double mass_coef = 0.0, const double* f = nullptr,
+                             double* rhs = nullptr, int rhs_add = 1);
 void assemble_elasticity_tet(Bsr& b, double lambda, double mu2, double c0, const double* f, double* rhs, int rhs_add);
 void apply_neumann(Mesh& m, int k, int mode, const double* v, int64_t n_faces, const int32_t* face_nodes,
                    const int32_t* face_cells, int mem, double* rhs);
@@ -568,6 +573,10 @@ void ls_point_update(LinearSystem& ls, int32_t row, int32_t col, double v, bool 
 // common value
 void ls_set_list(LinearSystem& ls, const int32_t* ids, int64_t n, int mem, int kind, double value, double penalty,
                  const double* dvalues = nullptr);
+// vectorial Dirichlet on nodes (owned ones): for every component i < nb_dof with
+// bit i of `mask` set, DoF nb_dof*node + i gets values[i] by `kind`; one launch
+void ls_set_vectorial(LinearSystem& ls, int nb_dof, const int32_t* nodes, int64_t n, int mem, int kind,
+                      const double* values, unsigned mask, double penalty);
 
 void mesh_structured(Ctx& ctx, Mesh& m, int dim, int n, int nz, double jitter, uint64_t seed, int nranks, int rank);
 void mesh_structured_bottom(Mesh& m, std::vector<int32_t>& ids);

@@ -2664,7 +2664,16 @@ __device__ __forceinline__ int64_t bidx2(bool per_block, int64_t rb4, int64_t nn
   return per_block ? rb4 + (int64_t)slot * 4 + i * 2 + j : rb4 + (int64_t)i * 2 * nnz_row + 2 * slot + j;
 }
 
-template <bool LDS>
+//
+// EXT (afem_bsr_assemble_elasticity_p1_ex): in the same pass, mass_coef x the
+// consistent P1 mass on the component diagonal (per triangle |K|/6 to the row
+// node's block, |K|/12 to each neighbour block: the 2D twin of the c0 term of
+// k_assemble_elast_tet) and the body force of modules/elasticity/FemModule.cc:
+// 230-241, rhs[2 row + i] = f_i (sum |K|) / 3 over the row's triangles, set or
+// added once per owned row (rows are owned nodes: the isOwn() filter), plain
+// stores.  The mass is added to the finished stiffness entry in an addition of
+// its own (add_nc): the stiffness part is evaluated as in the plain instance.
+template <bool LDS, bool EXT = false>
 __global__ __launch_bounds__(64) void k_assemble_elast_tri(int u_cap, int w_cap, int run, bool per_block,
                                                            const int32_t* __restrict__ perm,
                                                            const int64_t* __restrict__ row_ptr,
@@ -2678,7 +2687,8 @@ __global__ __launch_bounds__(64) void k_assemble_elast_tri(int u_cap, int w_cap,
                                                            const int64_t* __restrict__ snode_ptr,
                                                            const int32_t* __restrict__ snode,
                                                            const double* __restrict__ coords, double lambda,
-                                                           double mu2, double* __restrict__ vals)
+                                                           double mu2, double* __restrict__ vals, double mass_coef,
+                                                           double fx, double fy, double* __restrict__ rhs, int rhs_add)
 {
   extern __shared__ __align__(16) unsigned char smem[];
   Tile<2, 4, 0> tile(smem, u_cap, w_cap);
@@ -2714,6 +2724,7 @@ __global__ __launch_bounds__(64) void k_assemble_elast_tri(int u_cap, int w_cap,
   };
   if (active) {
     double d00 = 0, d01 = 0, d10 = 0, d11 = 0;
+    double macc = 0.0;  // EXT: sum of the row's triangle areas
     uint32_t dslot = 0xFFu;
     for (int k = 0; k < kmax; ++k) {
       const uint32_t e = ip[(int64_t)(k >> 2) * 256 + (k & 3)];
@@ -2728,16 +2739,23 @@ __global__ __launch_bounds__(64) void k_assemble_elast_tri(int u_cap, int w_cap,
       const double e1x = x1.x - x0.x, e1y = x1.y - x0.y, e2x = x2.x - x0.x, e2y = x2.y - x0.y;
       const double area = fabs(e1x * e2y - e2x * e1y) / 2.0;
       const double sc = 1.0 / (4.0 * area);
+      const double m12 = EXT ? mass_coef * area * (1.0 / 12.0) : 0.0;
+      if (EXT) macc += area;
       // row dof i of node 0, column dof j of node b:
       //  lam(i,j)  = (bx_i + by_i)(bx_j + by_j) over the interleaved B rows
       //  shr(i,j)  = bx_i bx_j + by_i by_j + 0.5 bs_i bs_j
       // with for dof (node a, comp 0): bx = px[a], by = 0, bs = py[a]
       //      for dof (node a, comp 1): bx = 0, by = py[a], bs = px[a]
       for (int nb = 0; nb < 3; ++nb) {
-        const double K00 = (lambda * (px[0] * px[nb])) * sc + (mu2 * (px[0] * px[nb] + 0.5 * py[0] * py[nb])) * sc;
+        double K00 = (lambda * (px[0] * px[nb])) * sc + (mu2 * (px[0] * px[nb] + 0.5 * py[0] * py[nb])) * sc;
         const double K01 = (lambda * (px[0] * py[nb])) * sc + (mu2 * (0.5 * py[0] * px[nb])) * sc;
         const double K10 = (lambda * (py[0] * px[nb])) * sc + (mu2 * (0.5 * px[0] * py[nb])) * sc;
-        const double K11 = (lambda * (py[0] * py[nb])) * sc + (mu2 * (py[0] * py[nb] + 0.5 * px[0] * px[nb])) * sc;
+        double K11 = (lambda * (py[0] * py[nb])) * sc + (mu2 * (py[0] * py[nb] + 0.5 * px[0] * px[nb])) * sc;
+        if (EXT) {
+          const double m = nb == 0 ? 2.0 * m12 : m12;
+          K00 = add_nc(K00, m);
+          K11 = add_nc(K11, m);
+        }
         if (nb == 0) {
           d00 += K00;
           d01 += K01;
@@ -2758,6 +2776,13 @@ __global__ __launch_bounds__(64) void k_assemble_elast_tri(int u_cap, int w_cap,
       put((int)dslot, 0, 1, d01);
       put((int)dslot, 1, 0, d10);
       put((int)dslot, 1, 1, d11);
+    }
+    if (EXT && rhs) {
+      const double a3 = macc * (1.0 / 3.0);
+      const double r0 = fx * a3, r1 = fy * a3;
+      double* const r = rhs + 2 * (int64_t)row;
+      r[0] = rhs_add ? add_nc(r[0], r0) : r0;
+      r[1] = rhs_add ? add_nc(r[1], r1) : r1;
     }
   }
   if (LDS) write_back<4>(tile, lane, run, active, rb, len, per_block, vals);
@@ -3391,7 +3416,8 @@ void assemble_elasticity_tet(Bsr& b, double lambda, double mu2, double c0, const
   b.last_kernel = AFEM_KERNEL_ELAST3_ITEM;
 }
 
-void assemble_elasticity_tri(Bsr& b, double lambda, double mu2)
+void assemble_elasticity_tri(Bsr& b, double lambda, double mu2, double mass_coef, const double* f, double* rhs,
+                             int rhs_add)
 {
   Structure& s = b.s;
   Ctx& ctx = *b.mesh->ctx;
@@ -3402,11 +3428,19 @@ void assemble_elasticity_tri(Bsr& b, double lambda, double mu2)
   const dim3 grid((unsigned)s.n_slices), blk(64);
 #define AFEM_EL_ARGS s.max_slice_nodes, s.max_slice_w, s.run, b.order_per_block, s.perm.p, s.row_ptr.p, s.cols.p, s.inc.p, \
                      s.inc_slice_ptr.p, s.inc_slice_k.p, s.slice_w.p, s.lidx_ptr.p, s.lidx.p, s.snode_ptr.p,         \
-                     s.snode.p, b.mesh->coords.p, lambda, mu2, b.values.p
-  if (lds)
-    hipLaunchKernelGGL(k_assemble_elast_tri<true>, grid, blk, (size_t)shm, ctx.stream, AFEM_EL_ARGS);
+                     s.snode.p, b.mesh->coords.p, lambda, mu2, b.values.p, mass_coef, f ? f[0] : 0.0,                \
+                     f ? f[1] : 0.0, f ? rhs : nullptr, rhs_add
+  // the extended instances only when there is mass or a body force: the plain
+  // entry (and the extended one without either) keeps its instance and its bits
+  const bool ext = mass_coef != 0.0 || f;
+  if (lds && ext)
+    hipLaunchKernelGGL((k_assemble_elast_tri<true, true>), grid, blk, (size_t)shm, ctx.stream, AFEM_EL_ARGS);
+  else if (lds)
+    hipLaunchKernelGGL((k_assemble_elast_tri<true, false>), grid, blk, (size_t)shm, ctx.stream, AFEM_EL_ARGS);
+  else if (ext)
+    hipLaunchKernelGGL((k_assemble_elast_tri<false, true>), grid, blk, 0, ctx.stream, AFEM_EL_ARGS);
   else
-    hipLaunchKernelGGL(k_assemble_elast_tri<false>, grid, blk, 0, ctx.stream, AFEM_EL_ARGS);
+    hipLaunchKernelGGL((k_assemble_elast_tri<false, false>), grid, blk, 0, ctx.stream, AFEM_EL_ARGS);
 #undef AFEM_EL_ARGS
   AFEM_LAUNCHED();
   b.last_kernel = AFEM_KERNEL_ELAST2;

@@ -534,12 +534,16 @@ int afem_bsr_assemble_elasticity_p1_ex(afem_bsr* b, double lambda, double mu2, d
   AFEM_RANGE("afem: BSRFormat::assembleBilinear (elasticity P1)");
   NOT_NULL(b);
   AFEM_REQUIRE(b->has_sparsity, AFEM_ERR_STATE, "assembleBilinear called before computeSparsity");
-  AFEM_REQUIRE(b->mesh->nv == 4 && b->nb_dof == 3, AFEM_ERR_NOT_IMPL,
-               "the mass / body-force form is implemented for NB_DOF = 3 on tetrahedra");
+  const bool tet3 = b->mesh->nv == 4 && b->nb_dof == 3, tri2 = b->mesh->nv == 3 && b->nb_dof == 2;
+  AFEM_REQUIRE(tet3 || tri2, AFEM_ERR_NOT_IMPL,
+               "the mass / body-force form is implemented for NB_DOF = 3 on tetrahedra and NB_DOF = 2 on triangles");
   AFEM_REQUIRE(!body_force || rhs, AFEM_ERR_ARG, "body_force given without an rhs array");
   AFEM_REQUIRE(rhs_mode == AFEM_RHS_ADD || rhs_mode == AFEM_RHS_SET, AFEM_ERR_ARG, "unknown rhs_mode");
   b->mesh->ctx->set_device();
-  assemble_elasticity_tet(*b, lambda, mu2, mass_coef, body_force, rhs, rhs_mode == AFEM_RHS_ADD ? 1 : 0);
+  if (tet3)
+    assemble_elasticity_tet(*b, lambda, mu2, mass_coef, body_force, rhs, rhs_mode == AFEM_RHS_ADD ? 1 : 0);
+  else
+    assemble_elasticity_tri(*b, lambda, mu2, mass_coef, body_force, rhs, rhs_mode == AFEM_RHS_ADD ? 1 : 0);
   API_END
 }
 
@@ -1169,6 +1173,35 @@ int afem_ls_dirichlet_row_elimination(afem_ls* ls, const int32_t* dofs, int64_t 
   API_END
 }
 
+int afem_ls_dirichlet_row_column_elimination(afem_ls* ls, const int32_t* dofs, int64_t n, double value, int mem)
+{
+  API_BEGIN
+  NOT_NULL(ls);
+  if (n > 0) NOT_NULL(dofs);
+  ls->ctx->set_device();
+  ls_set_list(*ls, dofs, n, mem, 2, value, 0.0);
+  API_END
+}
+
+int afem_ls_dirichlet_vectorial(afem_ls* ls, int nb_dof, const int32_t* nodes, int64_t n_nodes, const double* values,
+                                unsigned component_mask, int method, double penalty, int mem)
+{
+  API_BEGIN
+  NOT_NULL(ls);
+  NOT_NULL(values);
+  if (n_nodes > 0) NOT_NULL(nodes);
+  AFEM_REQUIRE(nb_dof >= 1 && nb_dof <= 3, AFEM_ERR_ARG, "applyDirichletVectorial: NB_DOF must be 1, 2 or 3");
+  AFEM_REQUIRE(ls->n_rows % nb_dof == 0, AFEM_ERR_ARG,
+               "applyDirichletVectorial: the linear system size is no multiple of NB_DOF");
+  AFEM_REQUIRE(method == AFEM_DIRICHLET_PENALTY || method == AFEM_DIRICHLET_ROW_ELIMINATION ||
+                   method == AFEM_DIRICHLET_ROW_COLUMN_ELIMINATION,
+               AFEM_ERR_ARG, "applyDirichletVectorial: unknown method");
+  AFEM_REQUIRE(mem == AFEM_MEM_HOST || mem == AFEM_MEM_DEVICE, AFEM_ERR_ARG, "applyDirichletVectorial: unknown mem");
+  ls->ctx->set_device();
+  ls_set_vectorial(*ls, nb_dof, nodes, n_nodes, mem, method, values, component_mask, penalty);
+  API_END
+}
+
 int afem_apply_neumann(afem_mesh* mesh, int nb_dof, int mode, const double value[3], int64_t n_faces,
                        const int32_t* face_nodes, const int32_t* face_cells, int mem, double* rhs)
 {
@@ -1239,6 +1272,7 @@ int afem_ls_clear_values(afem_ls* ls)
   ls->add_map.clear();
   ls->set_map.clear();
   ls->host_elim.clear();
+  ls->list_elim_rc = false;
   AFEM_HIP(hipMemsetAsync(ls->forced_info.p, 0, ls->forced_info.bytes(), ctx.stream));
   AFEM_HIP(hipMemsetAsync(ls->elim_info.p, 0, ls->elim_info.bytes(), ctx.stream));
   AFEM_HIP(hipMemsetAsync(ls->elim_value.p, 0, ls->elim_value.bytes(), ctx.stream));

@@ -51,6 +51,37 @@ __global__ void k_set_list(int64_t n, const int32_t* __restrict__ ids, int kind,
   }
 }
 
+// Vectorial Dirichlet on a node list, the four ...Vectorial helpers of
+// femutils/ArcaneFemFunctionsGpu.h:514-586 (face or point group: the caller
+// passes the group's nodes): one lane per listed node, every component whose
+// bit is set in `mask` gets its value by `kind` (as k_set_list); a cleared bit
+// is the reference's NULL.  Nodes >= n_own are skipped (isOwn()).
+__global__ void k_set_vectorial(int64_t n, const int32_t* __restrict__ nodes, int nb_dof, unsigned mask, int kind,
+                                double v0, double v1, double v2, double penalty, int64_t n_own,
+                                uint8_t* __restrict__ forced_info, double* __restrict__ forced_value,
+                                uint8_t* __restrict__ elim_info, double* __restrict__ elim_value,
+                                double* __restrict__ rhs)
+{
+  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int32_t v = nodes[t];
+  if (v < 0 || v >= n_own) return;
+  for (int i = 0; i < nb_dof; ++i) {
+    if (!((mask >> i) & 1u)) continue;
+    const int64_t d = (int64_t)nb_dof * v + i;
+    const double value = i == 0 ? v0 : (i == 1 ? v1 : v2);
+    if (kind == 0) {
+      forced_info[d] = 1;
+      forced_value[d] = penalty;
+      rhs[d] = penalty * value;
+    }
+    else {
+      elim_info[d] = (kind == 1) ? kElimRow : kElimRowCol;
+      elim_value[d] = value;
+    }
+  }
+}
+
 // Row+column elimination, phase 1 (Aleph _fillMatrix,
 // femutils/AlephDoFLinearSystem.cc:539-565): for every row+column eliminated
 // DoF i and every owned column j != i of row i, rhs_j -= A[i,j] * g_i (the
@@ -1413,16 +1444,30 @@ __global__ __launch_bounds__(kThreads) void k_dot(int64_t n, const double* __res
 // one rank their values are not unknowns of this system.
 constexpr int kDirectThreads = 1024;
 
+// An eliminated row is the equation x_d = g (k_apply_bcs).  With row
+// elimination alone the column of d keeps the other rows' entries: in the
+// dense copy they go to the right-hand side (b_r -= a_rd g), so the factored
+// matrix is the row+column eliminated one, the pivot of column d is its own
+// row and x_d comes back as g itself.  The CSR values are not modified.
 __global__ void k_csr_to_dense(int64_t n, const int64_t* __restrict__ rows, const int32_t* __restrict__ cols,
-                               const double* __restrict__ vals, const double* __restrict__ b, double* __restrict__ a)
+                               const double* __restrict__ vals, const double* __restrict__ b,
+                               const uint8_t* __restrict__ elim_info, const double* __restrict__ elim_value,
+                               double* __restrict__ a)
 {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
   double* ar = a + r * (n + 1);
   for (int64_t j = 0; j <= n; ++j) ar[j] = 0.0;
-  for (int64_t k = rows[r]; k < rows[r + 1]; ++k)
-    if (cols[k] < n) ar[cols[k]] += vals[k];
-  ar[n] = b[r];
+  double br = b[r];
+  for (int64_t k = rows[r]; k < rows[r + 1]; ++k) {
+    const int32_t c = cols[k];
+    if (c >= n) continue;
+    if (c != (int32_t)r && elim_info[c])
+      br -= vals[k] * elim_value[c];
+    else
+      ar[c] += vals[k];
+  }
+  ar[n] = br;
 }
 
 __global__ __launch_bounds__(kDirectThreads) void k_dense_gauss(int n, double* __restrict__ a, double* __restrict__ x,
@@ -1897,6 +1942,31 @@ void ls_set_list(LinearSystem& ls, const int32_t* ids, int64_t n, int mem, int k
                      dvalues, penalty, ls.n_rows, ls.forced_info.p, ls.forced_value.p, ls.elim_info.p, ls.elim_value.p,
                      ls.rhs.p);
   AFEM_LAUNCHED();
+  if (kind == 2) ls.list_elim_rc = true;
+  if (tmp.p) ctx.sync();
+}
+
+void ls_set_vectorial(LinearSystem& ls, int nb_dof, const int32_t* nodes, int64_t n, int mem, int kind,
+                      const double* values, unsigned mask, double penalty)
+{
+  Ctx& ctx = *ls.ctx;
+  mask &= (1u << nb_dof) - 1u;
+  if (n <= 0 || !mask) return;
+  const int32_t* dn = nodes;
+  DevBuf<int32_t> tmp;
+  if (mem == AFEM_MEM_HOST) {
+    tmp.alloc(n);
+    AFEM_HIP(hipMemcpyAsync(tmp.p, nodes, tmp.bytes(), hipMemcpyHostToDevice, ctx.stream));
+    dn = tmp.p;
+  }
+  double v[3] = { 0.0, 0.0, 0.0 };
+  for (int i = 0; i < nb_dof; ++i)
+    if ((mask >> i) & 1u) v[i] = values[i];
+  hipLaunchKernelGGL(k_set_vectorial, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, ctx.stream, n, dn, nb_dof, mask,
+                     kind, v[0], v[1], v[2], penalty, ls.n_rows / nb_dof, ls.forced_info.p, ls.forced_value.p,
+                     ls.elim_info.p, ls.elim_value.p, ls.rhs.p);
+  AFEM_LAUNCHED();
+  if (kind == 2) ls.list_elim_rc = true;
   if (tmp.p) ctx.sync();
 }
 
@@ -1974,8 +2044,9 @@ void ls_apply_bcs(LinearSystem& ls)
 {
   Ctx& ctx = *ls.ctx;
   require_csr(ls);
-  // row+column elimination needs a column pass first (only when present)
-  bool has_rc = false;
+  // row+column elimination needs a column pass first (only when present:
+  // requested row by row from the host, or by a device list)
+  bool has_rc = ls.list_elim_rc;
   for (auto& kv : ls.host_elim)
     if (kv.second.first == kElimRowCol) has_rc = true;
   if (has_rc) {
@@ -2019,7 +2090,7 @@ void ls_solve_direct(LinearSystem& ls, afem_solve_stats* st)
   sing.alloc(1);
   AFEM_HIP(hipEventRecord(ctx.ev0, ctx.stream));
   hipLaunchKernelGGL(k_csr_to_dense, dim3(grid_for(n, 256)), dim3(256), 0, ctx.stream, n, ls.csr_rows, ls.csr_cols,
-                     ls.csr_vals, ls.rhs.p, ls.dense.p);
+                     ls.csr_vals, ls.rhs.p, ls.elim_info.p, ls.elim_value.p, ls.dense.p);
   AFEM_LAUNCHED();
   hipLaunchKernelGGL(k_dense_gauss, dim3(1), dim3(kDirectThreads), 0, ctx.stream, (int)n, ls.dense.p, ls.sol.p, sing.p);
   AFEM_LAUNCHED();

@@ -212,10 +212,18 @@ int afem_bsr_assemble_elasticity_p1(afem_bsr* bsr, double lambda, double mu2);
  * c0 term of the Newmark / generalized-alpha LHS,
  * modules/elastodynamics/FemModule.cc:259,1285-1340) and, if body_force
  * (3 doubles, host) is given, the vectorial constant source
- * rhs[3n+i] = f_i |K| / 4 on owned nodes (femutils/ArcaneFemFunctionsGpu.h:514-586;
+ * rhs[3n+i] = f_i |K| / 4 on owned nodes (the 3D form of the body-force loop
+ * of modules/elasticity/FemModule.cc:220-241;
  * rhs: device, 3*n_own; rhs_mode AFEM_RHS_ADD / AFEM_RHS_SET as for the Poisson
  * source). afem_bsr_assemble_elasticity_p1 on a tetrahedral
- * block-3 matrix is this call with mass_coef = 0 and no body force. */
+ * block-3 matrix is this call with mass_coef = 0 and no body force.
+ * Block-2 matrices on triangles take the same call: mass_coef * consistent P1
+ * mass (|K|/6 on the node's own block, |K|/12 on a neighbour's, component
+ * diagonal) and body_force (2 doubles, host) as rhs[2n+i] = f_i |K| / 3 on
+ * owned nodes (modules/elasticity/FemModule.cc:230-241; rhs: device, 2*n_own),
+ * fused into the triangle kernel's pass; without mass and body force it is
+ * afem_bsr_assemble_elasticity_p1, bit for bit.  Other (cell, NB_DOF)
+ * combinations: AFEM_ERR_NOT_IMPL. */
 int afem_bsr_assemble_elasticity_p1_ex(afem_bsr* bsr, double lambda, double mu2, double mass_coef,
                                        const double* body_force, double* rhs, int rhs_mode);
 int afem_bsr_reset_values(afem_bsr* bsr);                       /* resetMatrixValues */
@@ -517,6 +525,24 @@ int afem_ls_elimination_value(afem_ls* ls, double** dptr);
 int afem_ls_dirichlet_penalty(afem_ls* ls, const int32_t* dofs, int64_t n, double value, double penalty, int mem);
 /* ...ViaRowElimination (femutils/ArcaneFemFunctionsGpu.h:461-482): elimination_info = 1, value. */
 int afem_ls_dirichlet_row_elimination(afem_ls* ls, const int32_t* dofs, int64_t n, double value, int mem);
+/* The list form of eliminateRowColumn: elimination_info = 2, value; the column
+ * pass runs at afem_ls_apply_boundary_conditions / afem_ls_solve.  One rank,
+ * owned columns (as afem_ls_eliminate_row_column). */
+int afem_ls_dirichlet_row_column_elimination(afem_ls* ls, const int32_t* dofs, int64_t n, double value, int mem);
+/* Vectorial Dirichlet with NULL components, the four helpers
+ * apply{,Point}DirichletVia{Penalty,RowElimination}Vectorial
+ * (femutils/ArcaneFemFunctionsGpu.h:514-586, called by
+ * modules/elasticity/FemModule.cc:157-191): for each component i < nb_dof with
+ * bit i of component_mask set and each listed node v < n_own (= n_rows /
+ * nb_dof), `method` is applied to DoF nb_dof*v + i with values[i]; a cleared
+ * bit is the reference's "NULL" (values[i] is not read).  One launch for all
+ * components.  nodes: the node group (of a face group or a point group), host
+ * or device by `mem`; values: nb_dof doubles, host. */
+#define AFEM_DIRICHLET_PENALTY 0
+#define AFEM_DIRICHLET_ROW_ELIMINATION 1
+#define AFEM_DIRICHLET_ROW_COLUMN_ELIMINATION 2
+int afem_ls_dirichlet_vectorial(afem_ls* ls, int nb_dof, const int32_t* nodes, int64_t n_nodes, const double* values,
+                                unsigned component_mask, int method, double penalty, int mem);
 /* Neumann / traction right-hand side on boundary faces (K15):
  * BoundaryConditions{2D,3D}::applyNeumannToRhs (femutils/ArcaneFemFunctionsGpu.h:612-674,
  * 703-766) and the elasticity traction term (modules/elasticity/FemModule.cc:244-273).
