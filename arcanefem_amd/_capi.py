@@ -112,6 +112,15 @@ class SolveStats(ctypes.Structure):
                 ("amg_setup_ms", ctypes.c_double), ("precond_ms", ctypes.c_double)]
 
 
+class PrecondLevel(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("levels", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("dims", ctypes.c_int32 * 3), ("slab", ctypes.c_int32 * 4), ("rows", ctypes.c_int64),
+                ("block_rows", ctypes.c_int64), ("nnz_blocks", ctypes.c_int64), ("n_agg", ctypes.c_int64),
+                ("omega", ctypes.c_double), ("distributed", ctypes.c_int32), ("dense", ctypes.c_int32),
+                ("has_f32", ctypes.c_int32), ("kcycle", ctypes.c_int32), ("sweeps", ctypes.c_int32),
+                ("coarse_sweeps", ctypes.c_int32), ("scale", ctypes.c_double)]
+
+
 class StepTiming(ctypes.Structure):
     _fields_ = [("assemble_ms", ctypes.c_double), ("rhs_ms", ctypes.c_double), ("bc_ms", ctypes.c_double),
                 ("solve_ms", ctypes.c_double), ("precond_ms", ctypes.c_double), ("update_ms", ctypes.c_double),
@@ -216,6 +225,10 @@ SIGNATURES = {
     "afem_ls_apply_boundary_conditions": [P],
     "afem_ls_clear_values": [P],
     "afem_ls_solve": [P, ctypes.POINTER(SolveStats)],
+    "afem_ls_precond_prepare": [P, ctypes.POINTER(I32)],
+    "afem_ls_precond_apply": [P, P, P],
+    "afem_ls_precond_level_info": [P, I32, ctypes.POINTER(PrecondLevel)],
+    "afem_ls_precond_level_copy": [P, I32, P, P, P, P, P, P, P, P, P],
     "afem_ls_spmv": [P, P, P],
     "afem_ls_destroy": [P],
     "afem_comm_unique_id": [P],

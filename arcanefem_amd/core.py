@@ -537,6 +537,63 @@ class DoFLinearSystem:
                     amg_coarse_rows=st.amg_coarse_rows, amg_complexity=st.amg_complexity,
                     amg_setup_ms=st.amg_setup_ms, precond_ms=st.precond_ms)
 
+    # ---- diagnostic: the multigrid / AMG preconditioner part by part (tests/test_gpu_precond_parts.py)
+    PRECOND_KINDS = {0: None, 1: "geometric", 2: "algebraic"}
+
+    def precondPrepare(self):
+        """Diagnostic: what solve() does before its first iteration (boundary
+        conditions, SpMV plan, dinv / constraint flags, the multigrid or AMG
+        hierarchy of the solver options).  Returns None, "geometric" or
+        "algebraic"."""
+        self._check_init()
+        k = ctypes.c_int32()
+        call("afem_ls_precond_prepare", self.impl, ctypes.byref(k))
+        return self.PRECOND_KINDS[k.value]
+
+    def precondApply(self, r_dptr: int, z_dptr: int):
+        """Diagnostic: z = M^-1 r once (device arrays of n_rows doubles), the
+        call the PCG makes per iteration."""
+        self._check_init()
+        call("afem_ls_precond_apply", self.impl, ctypes.c_void_p(r_dptr), ctypes.c_void_p(z_dptr))
+
+    def precondLevelInfo(self, level: int) -> dict:
+        """Diagnostic: afem_precond_level of one level of the built hierarchy."""
+        self._check_init()
+        o = C.PrecondLevel()
+        call("afem_ls_precond_level_info", self.impl, level, ctypes.byref(o))
+        return dict(kind=self.PRECOND_KINDS[o.kind], levels=o.levels, k=o.k, dims=tuple(o.dims), slab=tuple(o.slab),
+                    rows=o.rows, block_rows=o.block_rows, nnz_blocks=o.nnz_blocks, n_agg=o.n_agg, omega=o.omega,
+                    distributed=bool(o.distributed), dense=bool(o.dense), has_f32=bool(o.has_f32),
+                    kcycle=bool(o.kcycle), sweeps=o.sweeps, coarse_sweeps=o.coarse_sweeps, scale=o.scale)
+
+    def precondLevel(self, level: int) -> dict:
+        """Diagnostic: the level's info plus host copies of its arrays in the
+        level's own layout (include/arcanefem_amd.h, afem_precond_level):
+        row_ptr, columns, values, dinv, cons; algebraic levels: in_graph, and
+        above a coarser level agg, agg_ptr, members."""
+        o = self.precondLevelInfo(level)
+        alg = o["kind"] == "algebraic"
+        has_agg = alg and o["n_agg"] > 0
+        a = dict(row_ptr=np.zeros(o["block_rows"] + 1, np.int64), columns=np.zeros(o["nnz_blocks"], np.int32),
+                 values=np.zeros(o["nnz_blocks"] * o["k"] ** 2, np.float64), dinv=np.zeros(o["rows"], np.float64),
+                 cons=np.zeros(o["rows"], np.uint8))
+        if alg:
+            a["in_graph"] = np.zeros(o["rows"], np.uint8)
+        if has_agg:
+            a["agg"] = np.zeros(o["rows"], np.int32)
+            a["agg_ptr"] = np.zeros(o["n_agg"] + 1, np.int64)
+            a["members"] = np.zeros(o["rows"], np.int32)
+
+        def ptr(name):
+            return _ptr(a[name]) if name in a and a[name].size else None
+
+        call("afem_ls_precond_level_copy", self.impl, level, ptr("row_ptr"), ptr("columns"), ptr("values"),
+             ptr("dinv"), ptr("cons"), ptr("in_graph"), ptr("agg"), ptr("agg_ptr"), ptr("members"))
+        if has_agg:
+            a["members"] = a["members"][:a["agg_ptr"][-1]]
+        o.update(a)
+        return o
+
     def spmv(self, x_dptr: int, y_dptr: int):
         call("afem_ls_spmv", self.impl, ctypes.c_void_p(x_dptr), ctypes.c_void_p(y_dptr))
 

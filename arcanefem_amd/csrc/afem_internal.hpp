@@ -508,12 +508,18 @@ struct LinearSystem {
   std::unique_ptr<Multigrid, MgDeleter> mg;
   std::unique_ptr<Amg, AmgDeleter> amg;  // algebraic multigrid (amg.hip, afem_solver_opts.amg)
   std::shared_ptr<void> spmv_plan;       // the current solve's SpMV plan (linear_system.hip SpmvPlan)
+  int precond_kind = 0;  // the hierarchy the last solve / prepare built: 0 none, 1 geometric, 2 algebraic
 };
 
 // ------------------------------------------------------------------ kernels (host launchers)
 void exclusive_scan_i64(Ctx& ctx, const int64_t* in, int64_t* out, int64_t n, DevBuf<int64_t>* tmp_pool = nullptr);
 void exclusive_scan_i32_to_i64(Ctx& ctx, const int32_t* in, int64_t* out, int64_t n);
 int64_t read_i64(Ctx& ctx, const int64_t* d);
+// dense host matrices of the preconditioners' coarsest levels (row-major m x m):
+// symmetric up to rounding; the inverse of a general one (Gauss-Jordan, partial
+// pivoting; A destroyed; false: singular)
+bool host_dense_symmetric(int m, const std::vector<double>& A);
+bool host_dense_inverse(int m, std::vector<double>& A, std::vector<double>& inv);
 void device_minmax_i32(Ctx& ctx, const int32_t* a, int64_t n, int32_t* lo, int32_t* hi);
 
 // nb_dof = 1: a lattice mesh in a non-generator numbering gets the canonical
@@ -558,6 +564,24 @@ void ls_mapped_gather(LinearSystem& ls);
 void ls_mapped_scatter_back(LinearSystem& ls);
 void ls_mapped_point_update(LinearSystem& ls, int32_t row, int32_t col, double v, bool set);
 void ls_solve(LinearSystem& ls, afem_solve_stats* st);
+// diagnostic entries (afem_ls_precond_*): the solve's prelude alone (returns
+// LinearSystem::precond_kind), one application z = M^-1 r, and a level of the
+// hierarchy (info + device pointers; false: no such level)
+int ls_precond_prepare(LinearSystem& ls);
+void ls_precond_apply(LinearSystem& ls, const double* r, double* z);
+struct PrecondLevelView {
+  afem_precond_level info{};
+  const int64_t* rp = nullptr;  // info.block_rows + 1 (distributed AMG level: rows + 1)
+  const int32_t* ci = nullptr;  // info.nnz_blocks
+  const double* v = nullptr;    // info.nnz_blocks * k * k
+  const double* dinv = nullptr;  // info.rows
+  const uint8_t* in = nullptr;   // algebraic: info.rows
+  const int32_t* agg = nullptr;  // algebraic with a coarser level: info.rows
+  const int64_t* ap = nullptr;   // ... info.n_agg + 1
+  const int32_t* mem = nullptr;  // ... ap[n_agg]
+};
+bool mg_level_view(const LinearSystem& ls, int level, PrecondLevelView& out);
+bool amg_level_view(const LinearSystem& ls, int level, PrecondLevelView& out);
 void ls_spmv(LinearSystem& ls, const double* x, double* y);
 void ls_spmv_planned(LinearSystem& ls, const double* x, double* y);
 // algebraic multigrid preconditioner (amg.hip)

@@ -1484,6 +1484,19 @@ bool dense_inverse(Ctx& ctx, Amg& a, AmgLevel& L)
   }
   for (int i = 0; i < m; ++i)
     for (int j = 0; j < m; ++j) A[(size_t)i * m + j] *= sc[i] * sc[j];
+  // a non-symmetric operator (eliminated rows keep their columns): the general inverse, not
+  // the Cholesky factor of the lower triangle (multigrid.hip dense_inverse)
+  if (!host_dense_symmetric(m, A)) {
+    std::vector<double> inv;
+    if (!host_dense_inverse(m, A, inv)) return false;
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < m; ++j) inv[(size_t)i * m + j] *= sc[i] * sc[j];
+    a.ainv.alloc((size_t)m * m);
+    AFEM_HIP(hipMemcpyAsync(a.ainv.p, inv.data(), inv.size() * 8, hipMemcpyHostToDevice, ctx.stream));
+    ctx.sync();
+    a.n_dense = m;
+    return true;
+  }
   for (int j = 0; j < m; ++j) {
     double d = A[(size_t)j * m + j];
     for (int q = 0; q < j; ++q) d -= A[(size_t)j * m + q] * A[(size_t)j * m + q];
@@ -1959,6 +1972,44 @@ void amg_stats(const LinearSystem& ls, int32_t* levels, int64_t* coarse_rows, do
   double nz = 0.0;
   for (const auto& L : ls.amg->lv) nz += (double)L.nnz;
   *complexity = ls.amg->lv[0].nnz > 0 ? nz / (double)ls.amg->lv[0].nnz : 0.0;
+}
+
+// diagnostic (afem_ls_precond_level_*): level `level` as the cycle uses it
+bool amg_level_view(const LinearSystem& ls, int level, PrecondLevelView& out)
+{
+  if (!ls.amg || level < 0 || level >= (int)ls.amg->lv.size()) return false;
+  const Amg& a = *ls.amg;
+  const AmgLevel& L = a.lv[level];
+  const bool last = level + 1 == (int)a.lv.size();
+  afem_precond_level& o = out.info;
+  o = afem_precond_level{};
+  o.kind = AFEM_PRECOND_ALGEBRAIC;
+  o.levels = (int32_t)a.lv.size();
+  o.k = 1;
+  o.rows = L.n;
+  o.block_rows = L.n;
+  o.nnz_blocks = L.nnz;
+  // (a gathered next level: this rank's aggregates are a part of its rows)
+  o.n_agg = last || L.pass || !L.agg.p ? 0 : (L.gather_off >= 0 ? L.nc_local : a.lv[level + 1].n);
+  o.omega = L.omega;
+  o.distributed = L.dist ? 1 : 0;
+  o.dense = last && !L.dist && L.n > 0 && a.n_dense == L.n ? 1 : 0;
+  o.has_f32 = (level == 0 ? a.v32.p : L.v32.p) ? 1 : 0;
+  o.kcycle = L.kcoef.p ? 1 : 0;
+  o.sweeps = a.sweeps;
+  o.coarse_sweeps = level == 0 ? 2 * a.sweeps : kCoarseSweeps;
+  o.scale = a.scale;
+  out.rp = L.rp;
+  out.ci = L.ci;
+  out.v = L.v;
+  out.dinv = L.dinv.p;
+  out.in = L.in.p;
+  if (o.n_agg > 0) {
+    out.agg = L.agg.p;
+    out.ap = L.ap.p;
+    out.mem = L.mem.p;
+  }
+  return true;
 }
 
 }  // namespace afem

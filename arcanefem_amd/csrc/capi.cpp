@@ -1280,11 +1280,10 @@ int afem_ls_clear_values(afem_ls* ls)
   API_END
 }
 
-int afem_ls_solve(afem_ls* ls, afem_solve_stats* st)
+namespace {
+// the caller's live view into the device copy, as a solve reads it
+void ls_refresh_views(afem_ls* ls)
 {
-  API_BEGIN
-  AFEM_RANGE("afem: DoFLinearSystem::solve");
-  NOT_NULL(ls);
   if (ls->hv_vals && ls->has_csr && !ls->csr_from_coo && ls->csr_nnz > 0) {
     // host view: the values as they are now (the module may have edited its
     // view since setCSRValues; Hypre reads the live view at solve,
@@ -1298,9 +1297,104 @@ int afem_ls_solve(afem_ls* ls, afem_solve_stats* st)
     ls->ctx->set_device();
     ls_mapped_gather(*ls);
   }
+}
+}  // namespace
+
+int afem_ls_solve(afem_ls* ls, afem_solve_stats* st)
+{
+  API_BEGIN
+  AFEM_RANGE("afem: DoFLinearSystem::solve");
+  NOT_NULL(ls);
+  ls_refresh_views(ls);
   ls_solve(*ls, st);
   API_END
 }
+
+int afem_ls_precond_prepare(afem_ls* ls, int32_t* kind)
+{
+  API_BEGIN
+  NOT_NULL(ls);
+  ls_refresh_views(ls);
+  const int k = ls_precond_prepare(*ls);
+  if (kind) *kind = k;
+  API_END
+}
+
+int afem_ls_precond_apply(afem_ls* ls, const double* r, double* z)
+{
+  API_BEGIN
+  NOT_NULL(ls);
+  NOT_NULL(r);
+  NOT_NULL(z);
+  AFEM_REQUIRE(r != z, AFEM_ERR_ARG, "afem_ls_precond_apply: r and z must be different arrays");
+  ls_precond_apply(*ls, r, z);
+  API_END
+}
+
+namespace {
+void precond_level_view(afem_ls* ls, int32_t level, PrecondLevelView& v)
+{
+  const bool ok = ls->precond_kind == AFEM_PRECOND_GEOMETRIC   ? mg_level_view(*ls, level, v)
+                  : ls->precond_kind == AFEM_PRECOND_ALGEBRAIC ? amg_level_view(*ls, level, v)
+                                                               : false;
+  AFEM_REQUIRE(ok, AFEM_ERR_STATE, "no such level (no multigrid / AMG hierarchy built, or the level is out of range)");
+  if (v.info.nnz_blocks < 0) v.info.nnz_blocks = v.info.block_rows > 0 ? read_i64(*ls->ctx, v.rp + v.info.block_rows) : 0;
+}
+
+// n entries of `size` bytes to the host (a NULL dst: skipped)
+void level_to_host_bytes(Ctx& ctx, void* dst, const void* src, int64_t n, size_t size, const char* what)
+{
+  if (!dst) return;
+  AFEM_REQUIRE(src || n == 0, AFEM_ERR_STATE, what);
+  if (n > 0) AFEM_HIP(hipMemcpyAsync(dst, src, (size_t)n * size, hipMemcpyDeviceToHost, ctx.stream));
+}
+#define level_to_host(ctx, dst, src, n, what) level_to_host_bytes(ctx, dst, src, n, sizeof(*(dst)), what)
+}  // namespace
+
+int afem_ls_precond_level_info(afem_ls* ls, int32_t level, afem_precond_level* out)
+{
+  API_BEGIN
+  NOT_NULL(ls);
+  NOT_NULL(out);
+  ls->ctx->set_device();
+  PrecondLevelView v;
+  precond_level_view(ls, level, v);
+  *out = v.info;
+  API_END
+}
+
+int afem_ls_precond_level_copy(afem_ls* ls, int32_t level, int64_t* row_ptr, int32_t* columns, double* values,
+                               double* dinv, uint8_t* cons, uint8_t* in, int32_t* agg, int64_t* agg_ptr,
+                               int32_t* members)
+{
+  API_BEGIN
+  NOT_NULL(ls);
+  Ctx& ctx = *ls->ctx;
+  ctx.set_device();
+  PrecondLevelView v;
+  precond_level_view(ls, level, v);
+  const afem_precond_level& o = v.info;
+  level_to_host(ctx, row_ptr, v.rp, o.block_rows + 1, "the level has no row pointers");
+  level_to_host(ctx, columns, v.ci, o.nnz_blocks, "the level has no columns");
+  level_to_host(ctx, values, v.v, o.nnz_blocks * o.k * o.k, "the level has no values");
+  level_to_host(ctx, dinv, v.dinv, o.rows, "the level has no dinv");
+  if (cons) {
+    if (level == 0 && ls->cons.p && (int64_t)ls->cons.n >= o.rows && o.rows <= ls->n_rows)
+      level_to_host(ctx, cons, (const uint8_t*)ls->cons.p, o.rows, "");
+    else
+      std::memset(cons, 0, (size_t)o.rows);
+  }
+  level_to_host(ctx, in, v.in, o.rows, "in: not an algebraic level");
+  level_to_host(ctx, agg, v.agg, o.rows, "agg: not an algebraic level with a coarser level below");
+  level_to_host(ctx, agg_ptr, v.ap, o.n_agg + 1, "agg_ptr: not an algebraic level with a coarser level below");
+  if (members) {
+    AFEM_REQUIRE(v.mem && v.ap, AFEM_ERR_STATE, "members: not an algebraic level with a coarser level below");
+    level_to_host(ctx, members, v.mem, read_i64(ctx, v.ap + o.n_agg), "");
+  }
+  ctx.sync();
+  API_END
+}
+#undef level_to_host
 
 int afem_ls_spmv(afem_ls* ls, const double* x, double* y)
 {

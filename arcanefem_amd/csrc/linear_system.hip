@@ -2123,25 +2123,40 @@ void ls_solve_direct(LinearSystem& ls, afem_solve_stats* st)
 }
 }  // namespace
 
-void ls_solve(LinearSystem& ls, afem_solve_stats* st)
+namespace {
+// What a solve does before its first iteration -- the boundary conditions, the
+// SpMV plan, dinv / cons (block Jacobi: the inverse node blocks) and the
+// preconditioner's hierarchy -- and what the iteration needs from it.  Shared by
+// ls_solve and the diagnostic ls_precond_prepare: the same launches in the same order.
+struct SolvePrelude {
+  int method = AFEM_SOLVER_PCG;
+  bool multi = false;
+  SpmvPlan pl{};
+  unsigned vb = 1, vb3 = 1;
+  bool blk3 = false;
+  int64_t nb3 = 0;
+  bool use_gmg = false, use_amg = false;
+  double amg_setup_ms = 0.0;
+};
+
+SolvePrelude solve_prelude(LinearSystem& ls)
 {
+  SolvePrelude pre;
   Ctx& ctx = *ls.ctx;
   ctx.set_device();
+  ls.precond_kind = 0;
   if (!ls.has_csr && (!ls.add_map.empty() || !ls.set_map.empty() || !ls.host_elim.empty()))
     ls_build_from_host_coo(ls);
   require_csr(ls);
   AFEM_REQUIRE(ls.csr_n == ls.n_rows, AFEM_ERR_ARG, "CSR view row count differs from the linear system size");
   ls_apply_bcs(ls);
   const bool multi = ls.halo && ls.halo->comm && (comm_nranks(ls.halo->comm) > 1 || comm_self_loop());
+  pre.multi = multi;
   int method = ls.opts.method;
   if (method == AFEM_SOLVER_AUTO)  // femutils/DoFLinearSystem.cc:127-136: direct below 500 rows
     method = (!multi && ls.n_rows < 500 && ls.opts.fixed_iterations <= 0) ? AFEM_SOLVER_DIRECT : AFEM_SOLVER_PCG;
-  if (method == AFEM_SOLVER_DIRECT) {
-    AFEM_REQUIRE(!multi, AFEM_ERR_NOT_IMPL, "the direct solver runs on one rank (the reference's Sequential "
-                                            "solver refuses parallel runs, femutils/DoFLinearSystem.cc:562-564)");
-    ls_solve_direct(ls, st);
-    return;
-  }
+  pre.method = method;
+  if (method == AFEM_SOLVER_DIRECT) return pre;
 
   const int64_t n = ls.n_rows;
   if (ls.r.n != (size_t)n) {
@@ -2152,14 +2167,15 @@ void ls_solve(LinearSystem& ls, afem_solve_stats* st)
     ls.p.alloc(ls.n_cols);
     AFEM_HIP(hipMemsetAsync(ls.p.p, 0, ls.p.bytes(), ctx.stream));
   }
-  SpmvPlan pl = plan_spmv_ls(ctx, ls);
+  pre.pl = plan_spmv_ls(ctx, ls);
+  const SpmvPlan& pl = pre.pl;
   ls.spmv_plan = std::make_shared<SpmvPlan>(pl);  // the preconditioners' fine-level products (amg.hip)
   const int64_t n_part = 2 * std::max<int64_t>(pl.nblocks, kVecBlocks);
   if (ls.partial.n < (size_t)n_part) ls.partial.alloc(n_part);
   if (ls.cons.n != (size_t)n) ls.cons.alloc(n);
   if (ls.scal.n < 8) ls.scal.alloc(8);
   if (!ls.pinned) AFEM_HIP(hipHostMalloc(reinterpret_cast<void**>(&ls.pinned), 8 * sizeof(double), hipHostMallocDefault));
-  const unsigned vb = (unsigned)std::min<int64_t>(kVecBlocks, std::max<int64_t>(1, (n + kThreads - 1) / kThreads));
+  pre.vb = (unsigned)std::min<int64_t>(kVecBlocks, std::max<int64_t>(1, (n + kThreads - 1) / kThreads));
 
   AFEM_HIP(hipEventRecord(ctx.ev0, ctx.stream));
   if (pl.rpb == -2 && pl.blk_k == 3)
@@ -2174,9 +2190,11 @@ void ls_solve(LinearSystem& ls, afem_solve_stats* st)
                        ls.csr_cols, ls.csr_vals, ls.dinv.p, ls.cons.p);
   AFEM_LAUNCHED();
   const bool blk3 = ls.opts.precond_block == 3;
+  pre.blk3 = blk3;
   AFEM_REQUIRE(!blk3 || n % 3 == 0, AFEM_ERR_ARG, "block-Jacobi 3: the row count is not a multiple of 3");
   const int64_t nb3 = n / 3;
-  const unsigned vb3 = (unsigned)std::min<int64_t>(kVecBlocks, std::max<int64_t>(1, (nb3 + kThreads - 1) / kThreads));
+  pre.nb3 = nb3;
+  pre.vb3 = (unsigned)std::min<int64_t>(kVecBlocks, std::max<int64_t>(1, (nb3 + kThreads - 1) / kThreads));
   if (blk3) {
     if (ls.binv.n != (size_t)(9 * nb3)) ls.binv.alloc(9 * nb3 > 0 ? 9 * nb3 : 1);
     hipLaunchKernelGGL(k_inv_block3, dim3(grid_for(nb3, 256)), dim3(256), 0, ctx.stream, nb3, ls.csr_rows,
@@ -2185,17 +2203,61 @@ void ls_solve(LinearSystem& ls, afem_solve_stats* st)
   }
   // geometric multigrid (structured box, one rank); other systems: point Jacobi
   // (several ranks: block-Jacobi V-cycles on the slabs' owned blocks, mg_available)
-  const bool use_gmg = ls.opts.multigrid != 0 && !blk3 && mg_available(ls);
+  pre.use_gmg = ls.opts.multigrid != 0 && !blk3 && mg_available(ls);
   // algebraic multigrid where the geometric hierarchy does not exist (any mesh, one rank)
-  const bool use_amg = !use_gmg && ls.opts.amg != 0 && !blk3 && amg_available(ls);
-  const bool use_mg = use_gmg || use_amg;
-  if (use_gmg) mg_setup(ls);
-  double amg_setup_ms = 0.0;
-  if (use_amg) {
+  pre.use_amg = !pre.use_gmg && ls.opts.amg != 0 && !blk3 && amg_available(ls);
+  if (pre.use_gmg) mg_setup(ls);
+  if (pre.use_amg) {
     const auto t0 = std::chrono::steady_clock::now();
     if (amg_setup(ls))
-      amg_setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      pre.amg_setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
+  ls.precond_kind = pre.use_gmg ? 1 : (pre.use_amg ? 2 : 0);
+  return pre;
+}
+}  // namespace
+
+// diagnostic: the solve's prelude alone (afem_ls_precond_prepare); returns the
+// preconditioner it built (0 none: point / block Jacobi or the direct solver)
+int ls_precond_prepare(LinearSystem& ls)
+{
+  solve_prelude(ls);
+  ls.ctx->sync();
+  return ls.precond_kind;
+}
+
+// diagnostic: z = M^-1 r once, the PCG's own mg_apply / amg_apply call
+void ls_precond_apply(LinearSystem& ls, const double* r, double* z)
+{
+  ls.ctx->set_device();
+  AFEM_REQUIRE(ls.precond_kind == 1 ? ls.mg != nullptr : (ls.precond_kind == 2 && ls.amg != nullptr), AFEM_ERR_STATE,
+               "no multigrid / AMG hierarchy: call the prepare entry (or solve) with such a preconditioner first");
+  if (ls.precond_kind == 2)
+    amg_apply(ls, r, z);
+  else
+    mg_apply(ls, r, z);
+  ls.ctx->sync();
+}
+
+void ls_solve(LinearSystem& ls, afem_solve_stats* st)
+{
+  Ctx& ctx = *ls.ctx;
+  const SolvePrelude pre = solve_prelude(ls);
+  const bool multi = pre.multi;
+  if (pre.method == AFEM_SOLVER_DIRECT) {
+    AFEM_REQUIRE(!multi, AFEM_ERR_NOT_IMPL, "the direct solver runs on one rank (the reference's Sequential "
+                                            "solver refuses parallel runs, femutils/DoFLinearSystem.cc:562-564)");
+    ls_solve_direct(ls, st);
+    return;
+  }
+  const int64_t n = ls.n_rows;
+  const SpmvPlan& pl = pre.pl;
+  const unsigned vb = pre.vb, vb3 = pre.vb3;
+  const bool blk3 = pre.blk3;
+  const int64_t nb3 = pre.nb3;
+  const bool use_gmg = pre.use_gmg, use_amg = pre.use_amg;
+  const bool use_mg = use_gmg || use_amg;
+  const double amg_setup_ms = pre.amg_setup_ms;
   // the K-cycle makes the preconditioner nonlinear (its Krylov weights depend
   // on r): the flexible beta then (AFEM_CG_FLEX=0: Fletcher-Reeves)
   const char* fxe = variant("AFEM_CG_FLEX");

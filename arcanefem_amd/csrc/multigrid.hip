@@ -23,7 +23,8 @@
 //    AFEM_MG_F32; the PCG's own product stays fp64), on one rank with the mask
 //    fused into the first sweep and the constraint fix into the last (AFEM_MG_FUSE);
 //  * coarsest level: dense inverse (<= kDenseMax DoF, symmetric scaling +
-//    Cholesky on the host at setup), else 16 Jacobi sweeps;
+//    Cholesky on the host at setup; Gauss-Jordan where eliminated rows make the
+//    operator non-symmetric), else 16 Jacobi sweeps;
 //  * constraint rows (penalty / eliminated, the PCG's `cons` flags) are taken
 //    out of the cycle: z = F V(F r) + C D^-1 r (F free, C constraint masks), so
 //    the preconditioner stays SPD and eliminated rows keep a zero direction.
@@ -808,6 +809,19 @@ bool dense_inverse(Ctx& ctx, Multigrid& mg, MgLevel& L)
   }
   for (int i = 0; i < m; ++i)
     for (int j = 0; j < m; ++j) A[(size_t)i * m + j] *= sc[i] * sc[j];
+  // eliminated rows keep their columns (k_apply_bcs): P^T A P is then not symmetric and
+  // the Cholesky factor of its lower triangle is not its inverse -- the general inverse
+  if (!host_dense_symmetric(m, A)) {
+    std::vector<double> inv;
+    if (!host_dense_inverse(m, A, inv)) return false;
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < m; ++j) inv[(size_t)i * m + j] *= sc[i] * sc[j];
+    mg.ainv.alloc((size_t)m * m);
+    AFEM_HIP(hipMemcpyAsync(mg.ainv.p, inv.data(), inv.size() * 8, hipMemcpyHostToDevice, ctx.stream));
+    ctx.sync();
+    mg.n_dense = m;
+    return true;
+  }
   // Cholesky A = L L^T (lower, in place)
   for (int j = 0; j < m; ++j) {
     double d = A[(size_t)j * m + j];
@@ -1521,6 +1535,46 @@ void mg_apply(LinearSystem& ls, const double* r, double* z)
   AFEM_HIP(hipMemcpyAsync(z, L0.x.p, n * sizeof(double), hipMemcpyDeviceToDevice, ctx.stream));
   hipLaunchKernelGGL(k_mg_fix, dim3(g), dim3(256), 0, ctx.stream, n, ls.cons.p, r, ls.dinv.p, z);
   AFEM_LAUNCHED();
+}
+
+// diagnostic (afem_ls_precond_level_*): level `level` as the cycle uses it
+bool mg_level_view(const LinearSystem& ls, int level, PrecondLevelView& out)
+{
+  if (!ls.mg || level < 0 || level >= (int)ls.mg->lv.size()) return false;
+  const Multigrid& mg = *ls.mg;
+  const MgLevel& L = mg.lv[level];
+  const bool last = level + 1 == (int)mg.lv.size();
+  afem_precond_level& o = out.info;
+  o = afem_precond_level{};
+  o.kind = AFEM_PRECOND_GEOMETRIC;
+  o.levels = (int32_t)mg.lv.size();
+  o.k = mg.k;
+  const Dims d = L.dist ? L.gd : L.d;
+  o.dims[0] = d.nx;
+  o.dims[1] = d.ny;
+  o.dims[2] = d.nz;
+  if (L.dist) {
+    o.slab[0] = L.sm.k0;
+    o.slab[1] = L.sm.nown;
+    o.slab[2] = L.sm.glo;
+    o.slab[3] = L.sm.ghi;
+  }
+  o.rows = L.n;
+  o.block_rows = L.nn;
+  o.nnz_blocks = -1;  // read from row_ptr by the caller of this view
+  o.omega = L.omega;
+  o.distributed = L.dist ? 1 : 0;
+  o.dense = last && level > 0 && mg.n_dense == L.n ? 1 : 0;
+  o.has_f32 = L.v32.p ? 1 : 0;
+  o.kcycle = L.kcoef.p ? 1 : 0;
+  o.sweeps = mg.sweeps;
+  o.coarse_sweeps = level == 0 ? 2 * mg.sweeps : kCoarseSweeps;
+  o.scale = 1.0;
+  out.rp = L.bp;
+  out.ci = L.bc;
+  out.v = L.v;
+  out.dinv = L.dinv;
+  return true;
 }
 
 }  // namespace afem

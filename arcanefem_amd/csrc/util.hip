@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -224,6 +225,51 @@ int64_t read_i64(Ctx& ctx, const int64_t* d)
   AFEM_HIP(hipMemcpyAsync(&v, d, sizeof(int64_t), hipMemcpyDeviceToHost, ctx.stream));
   ctx.sync();
   return v;
+}
+
+// a dense m x m host matrix (row-major) is symmetric up to the rounding of its
+// sums: |a_ij - a_ji| <= 1e-10 sqrt(|a_ii a_jj|)
+bool host_dense_symmetric(int m, const std::vector<double>& A)
+{
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < i; ++j) {
+      const double d = std::fabs(A[(size_t)i * m + j] - A[(size_t)j * m + i]);
+      if (d > 1e-10 * std::sqrt(std::fabs(A[(size_t)i * m + i] * A[(size_t)j * m + j]))) return false;
+    }
+  return true;
+}
+
+// inverse of a general dense m x m host matrix by Gauss-Jordan elimination with
+// partial pivoting (A is destroyed); false: singular
+bool host_dense_inverse(int m, std::vector<double>& A, std::vector<double>& inv)
+{
+  inv.assign((size_t)m * m, 0.0);
+  for (int i = 0; i < m; ++i) inv[(size_t)i * m + i] = 1.0;
+  for (int c = 0; c < m; ++c) {
+    int p = c;
+    for (int i = c + 1; i < m; ++i)
+      if (std::fabs(A[(size_t)i * m + c]) > std::fabs(A[(size_t)p * m + c])) p = i;
+    if (!(std::fabs(A[(size_t)p * m + c]) > 1e-13)) return false;
+    if (p != c)
+      for (int j = 0; j < m; ++j) {
+        std::swap(A[(size_t)p * m + j], A[(size_t)c * m + j]);
+        std::swap(inv[(size_t)p * m + j], inv[(size_t)c * m + j]);
+      }
+    const double d = 1.0 / A[(size_t)c * m + c];
+    for (int j = 0; j < m; ++j) {
+      A[(size_t)c * m + j] *= d;
+      inv[(size_t)c * m + j] *= d;
+    }
+    for (int i = 0; i < m; ++i) {
+      const double f = A[(size_t)i * m + c];
+      if (i == c || f == 0.0) continue;
+      for (int j = 0; j < m; ++j) {
+        A[(size_t)i * m + j] -= f * A[(size_t)c * m + j];
+        inv[(size_t)i * m + j] -= f * inv[(size_t)c * m + j];
+      }
+    }
+  }
+  return true;
 }
 
 }  // namespace afem

@@ -573,6 +573,63 @@ int afem_ls_clear_values(afem_ls* ls);
  * With a communicator attached the SpMV exchanges ghost values and the dot
  * products are summed over ranks (RCCL). */
 int afem_ls_solve(afem_ls* ls, afem_solve_stats* stats);
+/* ---- diagnostic: the multigrid / AMG preconditioner part by part.  Not part of
+ * the reference's interface and not on any hot path; the tests hold every part
+ * of the hierarchy to an fp64 restatement through these.
+ *
+ * afem_ls_precond_prepare does what afem_ls_solve does before its first
+ * iteration (the same function): boundary conditions into the CSR, the SpMV
+ * plan, dinv / constraint flags, then the geometric or algebraic hierarchy
+ * according to the solver options.  *kind: AFEM_PRECOND_NONE (point / block
+ * Jacobi, or the direct solver was chosen), _GEOMETRIC or _ALGEBRAIC.  A solve
+ * after it gives the bits and the iteration count of the solve alone.
+ * afem_ls_precond_apply: z = M^-1 r once for device arrays of n_rows doubles
+ * (r is not changed, r != z) -- the call the PCG makes per iteration; needs a
+ * hierarchy (prepare or a solve), AFEM_ERR_STATE otherwise.  Collective over the
+ * ranks of a distributed system, as the solve is. */
+#define AFEM_PRECOND_NONE 0
+#define AFEM_PRECOND_GEOMETRIC 1
+#define AFEM_PRECOND_ALGEBRAIC 2
+int afem_ls_precond_prepare(afem_ls* ls, int32_t* kind);
+int afem_ls_precond_apply(afem_ls* ls, const double* r, double* z);
+/* One level of the hierarchy that was built (level 0: the system itself).
+ * Layout of a level's operator: a CSR over NODE rows -- row_ptr[block_rows + 1],
+ * columns[nnz_blocks] (node ids, sorted within a row) -- and per node row r of
+ * len = row_ptr[r+1] - row_ptr[r] blocks, k scalar rows of k * len values each
+ * (BSRFormat's CSR order): entry (u, v) of the row's t-th block is
+ *   values[k*k*row_ptr[r] + k*u*len + k*t + v],  scalar row k*r + u, column k*columns[t] + v.
+ * k = 1 (every algebraic level): the plain scalar CSR.  A distributed level holds
+ * this rank's owned rows; its columns are local ids (owned first, then ghosts). */
+typedef struct afem_precond_level {
+  int32_t kind;         /* AFEM_PRECOND_GEOMETRIC / _ALGEBRAIC */
+  int32_t levels;       /* levels of the hierarchy */
+  int32_t k;            /* DoF per node row */
+  int32_t dims[3];      /* geometric: cells per axis of the level's box (distributed: the global box) */
+  int32_t slab[4];      /* geometric, distributed: first owned node layer, owned layers, ghost layer below, above */
+  int64_t rows;         /* scalar rows (owned) = k * block_rows */
+  int64_t block_rows;   /* node rows */
+  int64_t nnz_blocks;   /* entries of columns; values holds nnz_blocks * k * k doubles */
+  int64_t n_agg;        /* algebraic: aggregates = rows of the next level (0: the coarsest level) */
+  double omega;         /* damped-Jacobi weight of the level's sweeps */
+  int32_t distributed;  /* rows cut over the ranks */
+  int32_t dense;        /* the coarsest level, solved by its dense inverse (else smoothed) */
+  int32_t has_f32;      /* the cycle's products on this level run on an fp32 copy of the values */
+  int32_t kcycle;       /* the level's coarse problem is solved by the K-cycle's two Krylov steps */
+  int32_t sweeps;       /* pre- and post-smoothing sweeps of the cycle */
+  int32_t coarse_sweeps; /* sweeps of a coarsest level that is not dense */
+  double scale;         /* algebraic: factor on the coarse correction of a V-cycle level (1 geometric) */
+} afem_precond_level;
+int afem_ls_precond_level_info(afem_ls* ls, int32_t level, afem_precond_level* out);
+/* Copies the level's arrays to the host, every value as fp64; a NULL pointer
+ * skips that array.  row_ptr[block_rows + 1], columns[nnz_blocks],
+ * values[nnz_blocks * k * k], dinv[rows]; cons[rows]: the PCG's constraint flags
+ * (level 0 only; zeros on the other levels).  Algebraic levels: in[rows] (row in
+ * the strength graph), and with n_agg > 0: agg[rows] (row -> aggregate, -1
+ * outside), agg_ptr[n_agg + 1] / members[rows in an aggregate] (the inverse of agg
+ * as a CSR over the aggregates); AFEM_ERR_STATE when asked for on other levels. */
+int afem_ls_precond_level_copy(afem_ls* ls, int32_t level, int64_t* row_ptr, int32_t* columns, double* values,
+                               double* dinv, uint8_t* cons, uint8_t* in, int32_t* agg, int64_t* agg_ptr,
+                               int32_t* members);
 /* y[0:n_rows] = A x (x of length n_cols_local, ghost part exchanged first when
  * a communicator is attached).  Device pointers. */
 int afem_ls_spmv(afem_ls* ls, const double* x, double* y);

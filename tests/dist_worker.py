@@ -31,6 +31,9 @@ DYN_MG = dict(n=8, nz=12, E=21e5, nu=0.28, rho=1.0, dt=1e-3, f=(0.0, -9.81, 1.0)
 # GPU), 2 ranks stacked in z, the bench's material / step / clamp
 DYN_C5 = dict(n=128, nz=256, E=21e5, nu=0.28, rho=1.0, dt=1e-3, f=(0.0, 0.0, -1.0), steps=3)
 # generalized alpha with Rayleigh damping: the RHS's stiffness SpMVs exchange their operand's ghosts too
+# the distributed hierarchy part by part: scalar -- fine level over the slabs, then the gathered 5 x 5 x 9 box
+# (225 rows, dense); block-3 -- one distributed coarse level (675 rows) before the gathered one (135 rows)
+MG_PARTS = dict(n=8, nz=16, coef=1.7, lam=21e5 * 0.28 / (1.28 * 0.44), mu2=21e5 / 1.28)
 DYN_DAMP = dict(etam=0.3, etak=1e-3, alpm=0.2, alpf=0.4, time_discretization="generalized-alpha")
 
 
@@ -277,6 +280,58 @@ def main():
                                   rtol=1e-14, preconditioner="multigrid")
             res["iters_single"] = np.array([s1.step()["iterations"] for _ in range(p["steps"])])
             s1.close()
+    elif case in ("mg_parts", "mg_parts_b3"):
+        # the distributed geometric hierarchy part by part (tests/test_gpu_precond_parts.py): prepare,
+        # every level's owned rows and omega, one application of a right-hand side given by global DoF;
+        # rank 0 also does the same on ONE rank for the same global box
+        import precond_ref
+
+        k = 3 if case == "mg_parts_b3" else 1
+        n, nz = MG_PARTS["n"], MG_PARTS["nz"]
+        af.set_variant("AFEM_MG_F32", "0")  # the cycle in fp64
+        r_glob = precond_ref.hashed_vector(k * (n + 1) * (n + 1) * (nz + 1), 7)
+
+        def run(mesh, cm, prefix):
+            bsr = af.BSRFormat(mesh, k).initialize(True)
+            bsr.computeSparsity()
+            ls = af.DoFLinearSystem().initialize(ctx, k * mesh.n_own_nodes, k * mesh.n_nodes)
+            if k == 1:
+                bsr.assemblePoissonP1(MG_PARTS["coef"], 5.5, ls.rhsVariable(), rhs_mode="set")
+            else:
+                bsr.assembleElasticityP1Ex(MG_PARTS["lam"], MG_PARTS["mu2"], 0.0, (0.0, 0.0, -1.0), ls.rhsVariable(),
+                                           rhs_mode="set")
+            bsr.toLinearSystem(ls)
+            dofs = (k * mesh.bottom_nodes().astype(np.int64)[:, None] + np.arange(k)[None, :]).ravel().astype(np.int32)
+            if dofs.size:
+                ls.applyDirichletViaPenalty(dofs, 0.0, 1e30)
+            if cm is not None:
+                ls.set_halo_mesh(cm, mesh)
+            ls.setSolverOptions(rtol=1e-12, max_iter=5000, method="pcg", preconditioner="multigrid")
+            assert ls.precondPrepare() == "geometric"
+            _, _, l2g_ = mesh.download()
+            n_lv = ls.precondLevelInfo(0)["levels"]
+            res[prefix + "levels"] = n_lv
+            for l in range(n_lv):
+                for key, val in ls.precondLevel(l).items():
+                    res[f"{prefix}L{l}_{key}"] = np.asarray({"geometric": 1, "algebraic": 2}[val] if key == "kind" else val)
+            own = l2g_[:mesh.n_own_nodes]
+            r = r_glob[(k * own[:, None] + np.arange(k)[None, :]).ravel()]
+            d = ctx.malloc(8 * 2 * r.size)
+            ctx.to_device(d, r)
+            ls.precondApply(d, d + 8 * r.size)
+            res[prefix + "z"] = ctx.to_host(d + 8 * r.size, r.size, np.float64)
+            res[prefix + "l2g"] = l2g_
+            res[prefix + "n_own"] = mesh.n_own_nodes
+            ctx.free(d)
+            bsr.close()
+
+        mesh = af.Mesh.structured(ctx, 3, n, nz=nz, jitter=0.2, seed=20250220, nranks=world, rank=rank)
+        run(mesh, comm, "")
+        dist.barrier()
+        if rank == 0:
+            m1 = af.Mesh.structured(ctx, 3, n, nz=nz, jitter=0.2, seed=20250220)
+            run(m1, None, "one_")
+        dist.barrier()
     else:
         raise SystemExit(f"unknown case {case}")
     assert not comm.errors, comm.errors
