@@ -274,6 +274,26 @@ class BSRFormat:
         call("afem_bsr_assemble_elasticity_p1_ex", self.h, lam, mu2, mass_coef, f,
              ctypes.c_void_p(rhs_dptr) if rhs_dptr else None, _rhs_mode(rhs_mode))
 
+    def assembleElastodynamicsP1(self, c, body_force, u_dptr: int, v_dptr: int, a_dptr: int, fixed_dptr: int | None,
+                                 rhs_dptr: int, rhs_mode: str = "set"):
+        """Block-2 triangles, the fused step of the 2D elastodynamics module:
+        values = c[0] M + K(c[1], c[2]) and the complete dynamic right-hand
+        side from U, V, A (device, 2 per local node) in one pass; c = the
+        module's c0 .. c10, body_force = (f1, f2) or None, fixed_dptr = one
+        byte per owned DoF (or None): flagged DoFs get 0 ("set") or stay
+        untouched ("add")."""
+        if len(c) != 11:
+            raise ValueError("c needs the 11 constants c0 .. c10")
+        cc = (ctypes.c_double * 11)(*[float(x) for x in c])
+        f = None
+        if body_force is not None:
+            if len(body_force) != 2:
+                raise ValueError("body_force needs 2 components")
+            f = (ctypes.c_double * 2)(*[0.0 if x is None else float(x) for x in body_force])
+        call("afem_bsr_assemble_elastodynamics_p1", self.h, cc, f, ctypes.c_void_p(u_dptr), ctypes.c_void_p(v_dptr),
+             ctypes.c_void_p(a_dptr), ctypes.c_void_p(fixed_dptr) if fixed_dptr else None, ctypes.c_void_p(rhs_dptr),
+             _rhs_mode(rhs_mode))
+
     def resetMatrixValues(self):
         call("afem_bsr_reset_values", self.h)
 

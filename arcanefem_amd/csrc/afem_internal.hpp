@@ -538,6 +538,11 @@ void cube_row_stride(const Mesh& m, Structure& s, int nb_dof);  // sets s.cube_r
 // block-2 triangles: + mass_coef x consistent mass, body force f[2] into rhs (2 per owned node) when f is given
 void assemble_elasticity_tri(Bsr& b, double lambda, double mu2, double mass_coef = 0.0, const double* f = nullptr,
                              double* rhs = nullptr, int rhs_add = 1);
+// block-2 triangles, the fused elastodynamics step: values = c[0] M + K(c[1], c[2]) (the bits of
+// assemble_elasticity_tri) and rhs = body force + M Wm + K_lambda Wl + K_mu Wu from u, v, a
+// (device, 2 per local node), DoFs flagged in fixed (device, 2 per owned node, or null) masked
+void assemble_elastodynamics_tri(Bsr& b, const double c[11], const double* f, const double* u, const double* v,
+                                 const double* a, const uint8_t* fixed, double* rhs, int rhs_add);
 void assemble_elasticity_tet(Bsr& b, double lambda, double mu2, double c0, const double* f, double* rhs, int rhs_add);
 void apply_neumann(Mesh& m, int k, int mode, const double* v, int64_t n_faces, const int32_t* face_nodes,
                    const int32_t* face_cells, int mem, double* rhs);
@@ -640,6 +645,30 @@ struct Elastodynamics {
   DevBuf<int32_t> imp_ids;  // imposed displacements (afem_elastodynamics_set_dirichlet): owned DoFs
   DevBuf<double> imp_vals;  //   and their values
   int64_t n = 0, n_cols = 0;
+  // nb = 2: the 2D loop on triangles (modules/elastodynamics itself).  K is block-2; one fused
+  // kernel per step writes the LHS and the complete RHS from U, V, A (assemble_elastodynamics_tri):
+  // no mvals / klvals / kmvals, no lsm / lsl / lsu.  The Dirichlet conditions are kept as the
+  // deck's blocks (replayed in order through ls_set_vectorial every step), as flags for the
+  // kernel's and the tractions' guards (fixed2) and as imp_ids / imp_vals for the re-imposition.
+  int nb = 3;
+  double t = 0.0;  // time of the next step (FemModule.cc:175, :189)
+  struct Dirichlet2 {
+    DevBuf<int32_t> nodes;
+    double v[2] = { 0, 0 };
+    unsigned mask = 0;
+  };
+  std::vector<Dirichlet2> dir2;
+  int dir_method = -1;  // AFEM_DIRICHLET_* of the registered conditions (-1: none yet)
+  std::map<int32_t, double> dir_dofs;  // DoF -> value over all blocks, later ones overriding
+  DevBuf<uint8_t> fixed2;              // [2 n_own]
+  struct Traction2 {
+    DevBuf<int32_t> nodes;  // the group's owned nodes, each once
+    DevBuf<double> w;       // sum of |e| / 2 over the group's edges at the node
+    double t[2] = { 0, 0 };
+    unsigned mask = 0;
+    std::vector<double> times, values;  // CaseTable (values: 2 per time); empty: constant
+  };
+  std::vector<Traction2> trac2;
   afem_solve_stats last{};
   // afem_elastodynamics_profile: per-phase events of every step
   bool profile = false;
@@ -652,12 +681,23 @@ void dyn_step(Elastodynamics* d, afem_solve_stats* st);
 void dyn_set_dirichlet(Elastodynamics* d, const int32_t* dofs, const double* values, int64_t n, int mem);
 void dyn_set_time_step(Elastodynamics* d, double dt);
 void dyn_profile(Elastodynamics* d, bool on);
+// the 2D loop's registrations (AFEM_ERR_NOT_IMPL on a 3D handle)
+void dyn_set_lame(Elastodynamics* d, double lambda, double mu);
+void dyn_set_dirichlet_vectorial(Elastodynamics* d, const int32_t* nodes, int64_t n, const double values[2],
+                                 unsigned mask, int method, int mem);
+void dyn_set_traction(Elastodynamics* d, const int32_t* face_nodes, int64_t n_faces, const double t[2], unsigned mask,
+                      int mem);
+void dyn_set_traction_table(Elastodynamics* d, int index, const double* times, const double* values, int64_t n);
+// CaseTable::CurveLinear: piecewise linear in (times, values[n][2]), constant outside
+void table_interp2(const std::vector<double>& times, const std::vector<double>& values, double t, double out[2]);
 void dyn_destroy(Elastodynamics* d);
 
 void vec_lincomb(Ctx& ctx, int64_t n, double a, const double* x, double b, const double* y, double c, const double* z,
                  double* out);
 void newmark_update(Ctx& ctx, int64_t n, double dt, double beta, double gamma, const double* un, double* u, double* v,
                     double* a);
+void traction2_add(Ctx& ctx, int64_t n, const int32_t* nodes, const double* w, const double t[2], unsigned mask,
+                   const uint8_t* fixed, double* rhs);
 // x[ids[i]] = vals[i] (device arrays)
 void vec_scatter(Ctx& ctx, int64_t n, const int32_t* ids, const double* vals, double* x);
 

@@ -2673,7 +2673,32 @@ __device__ __forceinline__ int64_t bidx2(bool per_block, int64_t rb4, int64_t nn
 // added once per owned row (rows are owned nodes: the isOwn() filter), plain
 // stores.  The mass is added to the finished stiffness entry in an addition of
 // its own (add_nc): the stiffness part is evaluated as in the plain instance.
-template <bool LDS, bool EXT = false>
+//
+// DYN (afem_bsr_assemble_elastodynamics_p1, MODE 2 / 3): the EXT values (c0 M +
+// K(c1, c2), the same expressions) and, in the same pass, the complete dynamic
+// right-hand side of modules/elastodynamics/FemModule.cc:645-867.  The lane
+// that owns node row r has each incident triangle's gradients and area in
+// registers; it gathers U, V, A of the triangle's nodes through the row's
+// columns (global loads, in both instances: the LDS tile keeps coordinates and
+// accumulators only) and adds, in incidence order,
+//   m_rb Wm_b + Klambda_(r,.)(b,.) Wl_b + Kmu_(r,.)(b,.) Wu_b,   b over the triangle,
+// with Wm = c0 U + c3 V + c4 A, Wl = -c5 U + c7 V + c8 A, Wu = -c6 U + c9 V +
+// c10 A (the cell loop :842-862 regrouped by linearity), m_rb = |K|/6 (b = r)
+// or |K|/12, Klambda / Kmu the lambda = 1 / 2 mu = 1 parts of the element
+// matrix.  The row's stiffness terms factor through four sums per triangle:
+//   div = sum_b px_b Wl_b0 + py_b Wl_b1,  sx = sum_b px_b Wu_b0,  sy = sum_b py_b Wu_b1,
+//   sh = sum_b py_b Wu_b0 + px_b Wu_b1:
+//   rhs_0 += [px_r (div + sx) + py_r sh / 2] / 4|K|,  rhs_1 += [py_r (div + sy) + px_r sh / 2] / 4|K|.
+// MODE 2 is the undamped Newmark step (c5 .. c10 = 0): the mass part only.
+// fixed[2 n_own] (may be NULL) masks DoFs as the reference's m_u*_fixed guards:
+// 0 in set mode, untouched in add mode.  One plain store per DoF.
+struct ElastDyn {
+  double cm[3], cl[3], cu[3];  // weights of (U, V, A) in Wm, Wl, Wu
+  const double *u, *v, *a;     // [2 n_nodes]
+  const uint8_t* fixed;        // [2 n_own] or NULL
+};
+
+template <bool LDS, int MODE = 0>
 __global__ __launch_bounds__(64) void k_assemble_elast_tri(int u_cap, int w_cap, int run, bool per_block,
                                                            const int32_t* __restrict__ perm,
                                                            const int64_t* __restrict__ row_ptr,
@@ -2688,8 +2713,10 @@ __global__ __launch_bounds__(64) void k_assemble_elast_tri(int u_cap, int w_cap,
                                                            const int32_t* __restrict__ snode,
                                                            const double* __restrict__ coords, double lambda,
                                                            double mu2, double* __restrict__ vals, double mass_coef,
-                                                           double fx, double fy, double* __restrict__ rhs, int rhs_add)
+                                                           double fx, double fy, double* __restrict__ rhs, int rhs_add,
+                                                           ElastDyn dyn)
 {
+  constexpr bool EXT = MODE >= 1, DYN = MODE >= 2, DYNK = MODE == 3;
   extern __shared__ __align__(16) unsigned char smem[];
   Tile<2, 4, 0> tile(smem, u_cap, w_cap);
   const int lane = threadIdx.x;
@@ -2726,6 +2753,25 @@ __global__ __launch_bounds__(64) void k_assemble_elast_tri(int u_cap, int w_cap,
     double d00 = 0, d01 = 0, d10 = 0, d11 = 0;
     double macc = 0.0;  // EXT: sum of the row's triangle areas
     uint32_t dslot = 0xFFu;
+    // DYN: (Wm, Wl, Wu) of a node, two components each; the row node's once
+    struct W6 {
+      double m0, m1, l0, l1, u0, u1;
+    };
+    auto gather = [&](int32_t node) {
+      const int64_t o = 2 * (int64_t)node;
+      const double u0 = dyn.u[o], u1 = dyn.u[o + 1], v0 = dyn.v[o], v1 = dyn.v[o + 1], a0 = dyn.a[o], a1 = dyn.a[o + 1];
+      W6 w{ dyn.cm[0] * u0 + dyn.cm[1] * v0 + dyn.cm[2] * a0, dyn.cm[0] * u1 + dyn.cm[1] * v1 + dyn.cm[2] * a1, 0, 0, 0, 0 };
+      if (DYNK) {
+        w.l0 = dyn.cl[0] * u0 + dyn.cl[1] * v0 + dyn.cl[2] * a0;
+        w.l1 = dyn.cl[0] * u1 + dyn.cl[1] * v1 + dyn.cl[2] * a1;
+        w.u0 = dyn.cu[0] * u0 + dyn.cu[1] * v0 + dyn.cu[2] * a0;
+        w.u1 = dyn.cu[0] * u1 + dyn.cu[1] * v1 + dyn.cu[2] * a1;
+      }
+      return w;
+    };
+    W6 w0{};
+    if (DYN) w0 = gather(row);
+    double racc0 = 0.0, racc1 = 0.0;
     for (int k = 0; k < kmax; ++k) {
       const uint32_t e = ip[(int64_t)(k >> 2) * 256 + (k & 3)];
       if (e == kPad) break;
@@ -2741,6 +2787,20 @@ __global__ __launch_bounds__(64) void k_assemble_elast_tri(int u_cap, int w_cap,
       const double sc = 1.0 / (4.0 * area);
       const double m12 = EXT ? mass_coef * area * (1.0 / 12.0) : 0.0;
       if (EXT) macc += area;
+      if (DYN) {
+        const W6 w1 = gather(crow[s[0]]), w2 = gather(crow[s[1]]);
+        const double a12 = area * (1.0 / 12.0);
+        racc0 += a12 * (2.0 * w0.m0 + w1.m0 + w2.m0);
+        racc1 += a12 * (2.0 * w0.m1 + w1.m1 + w2.m1);
+        if (DYNK) {
+          const double div = px[0] * w0.l0 + py[0] * w0.l1 + px[1] * w1.l0 + py[1] * w1.l1 + px[2] * w2.l0 + py[2] * w2.l1;
+          const double sx = px[0] * w0.u0 + px[1] * w1.u0 + px[2] * w2.u0;
+          const double sy = py[0] * w0.u1 + py[1] * w1.u1 + py[2] * w2.u1;
+          const double sh = py[0] * w0.u0 + px[0] * w0.u1 + py[1] * w1.u0 + px[1] * w1.u1 + py[2] * w2.u0 + px[2] * w2.u1;
+          racc0 += (px[0] * (div + sx) + 0.5 * py[0] * sh) * sc;
+          racc1 += (py[0] * (div + sy) + 0.5 * px[0] * sh) * sc;
+        }
+      }
       // row dof i of node 0, column dof j of node b:
       //  lam(i,j)  = (bx_i + by_i)(bx_j + by_j) over the interleaved B rows
       //  shr(i,j)  = bx_i bx_j + by_i by_j + 0.5 bs_i bs_j
@@ -2777,7 +2837,21 @@ __global__ __launch_bounds__(64) void k_assemble_elast_tri(int u_cap, int w_cap,
       put((int)dslot, 1, 0, d10);
       put((int)dslot, 1, 1, d11);
     }
-    if (EXT && rhs) {
+    if (DYN) {
+      const double a3 = macc * (1.0 / 3.0);
+      const double r0 = fx * a3 + racc0, r1 = fy * a3 + racc1;
+      double* const r = rhs + 2 * (int64_t)row;
+      const bool f0 = dyn.fixed && dyn.fixed[2 * (int64_t)row], f1 = dyn.fixed && dyn.fixed[2 * (int64_t)row + 1];
+      if (rhs_add) {
+        if (!f0) r[0] = add_nc(r[0], r0);
+        if (!f1) r[1] = add_nc(r[1], r1);
+      }
+      else {
+        r[0] = f0 ? 0.0 : r0;
+        r[1] = f1 ? 0.0 : r1;
+      }
+    }
+    else if (EXT && rhs) {
       const double a3 = macc * (1.0 / 3.0);
       const double r0 = fx * a3, r1 = fy * a3;
       double* const r = rhs + 2 * (int64_t)row;
@@ -3429,18 +3503,50 @@ void assemble_elasticity_tri(Bsr& b, double lambda, double mu2, double mass_coef
 #define AFEM_EL_ARGS s.max_slice_nodes, s.max_slice_w, s.run, b.order_per_block, s.perm.p, s.row_ptr.p, s.cols.p, s.inc.p, \
                      s.inc_slice_ptr.p, s.inc_slice_k.p, s.slice_w.p, s.lidx_ptr.p, s.lidx.p, s.snode_ptr.p,         \
                      s.snode.p, b.mesh->coords.p, lambda, mu2, b.values.p, mass_coef, f ? f[0] : 0.0,                \
-                     f ? f[1] : 0.0, f ? rhs : nullptr, rhs_add
+                     f ? f[1] : 0.0, f ? rhs : nullptr, rhs_add, ElastDyn{}
   // the extended instances only when there is mass or a body force: the plain
   // entry (and the extended one without either) keeps its instance and its bits
   const bool ext = mass_coef != 0.0 || f;
   if (lds && ext)
-    hipLaunchKernelGGL((k_assemble_elast_tri<true, true>), grid, blk, (size_t)shm, ctx.stream, AFEM_EL_ARGS);
+    hipLaunchKernelGGL((k_assemble_elast_tri<true, 1>), grid, blk, (size_t)shm, ctx.stream, AFEM_EL_ARGS);
   else if (lds)
-    hipLaunchKernelGGL((k_assemble_elast_tri<true, false>), grid, blk, (size_t)shm, ctx.stream, AFEM_EL_ARGS);
+    hipLaunchKernelGGL((k_assemble_elast_tri<true, 0>), grid, blk, (size_t)shm, ctx.stream, AFEM_EL_ARGS);
   else if (ext)
-    hipLaunchKernelGGL((k_assemble_elast_tri<false, true>), grid, blk, 0, ctx.stream, AFEM_EL_ARGS);
+    hipLaunchKernelGGL((k_assemble_elast_tri<false, 1>), grid, blk, 0, ctx.stream, AFEM_EL_ARGS);
   else
-    hipLaunchKernelGGL((k_assemble_elast_tri<false, false>), grid, blk, 0, ctx.stream, AFEM_EL_ARGS);
+    hipLaunchKernelGGL((k_assemble_elast_tri<false, 0>), grid, blk, 0, ctx.stream, AFEM_EL_ARGS);
+#undef AFEM_EL_ARGS
+  AFEM_LAUNCHED();
+  b.last_kernel = AFEM_KERNEL_ELAST2;
+}
+
+void assemble_elastodynamics_tri(Bsr& b, const double c[11], const double* f, const double* u, const double* v,
+                                 const double* a, const uint8_t* fixed, double* rhs, int rhs_add)
+{
+  Structure& s = b.s;
+  Ctx& ctx = *b.mesh->ctx;
+  AFEM_REQUIRE(b.nb_dof == 2 && b.mesh->nv == 3, AFEM_ERR_NOT_IMPL,
+               "the fused elastodynamics step is implemented for NB_DOF = 2 on triangles (the reference's "
+               "elastodynamics module)");
+  const int64_t shm = tile_bytes(2, 4, s.max_slice_nodes, s.max_slice_w);
+  const bool lds = shm <= kTileLdsMax;
+  const dim3 grid((unsigned)s.n_slices), blk(64);
+  const ElastDyn dyn{ { c[0], c[3], c[4] }, { -c[5], c[7], c[8] }, { -c[6], c[9], c[10] }, u, v, a, fixed };
+  // the stiffness terms of the right-hand side only with damping or alpf (c5 .. c10)
+  bool full = false;
+  for (int i = 5; i <= 10; ++i) full = full || c[i] != 0.0;
+#define AFEM_EL_ARGS s.max_slice_nodes, s.max_slice_w, s.run, b.order_per_block, s.perm.p, s.row_ptr.p, s.cols.p, s.inc.p, \
+                     s.inc_slice_ptr.p, s.inc_slice_k.p, s.slice_w.p, s.lidx_ptr.p, s.lidx.p, s.snode_ptr.p,         \
+                     s.snode.p, b.mesh->coords.p, c[1], c[2], b.values.p, c[0], f ? f[0] : 0.0, f ? f[1] : 0.0, rhs, \
+                     rhs_add, dyn
+  if (lds && full)
+    hipLaunchKernelGGL((k_assemble_elast_tri<true, 3>), grid, blk, (size_t)shm, ctx.stream, AFEM_EL_ARGS);
+  else if (lds)
+    hipLaunchKernelGGL((k_assemble_elast_tri<true, 2>), grid, blk, (size_t)shm, ctx.stream, AFEM_EL_ARGS);
+  else if (full)
+    hipLaunchKernelGGL((k_assemble_elast_tri<false, 3>), grid, blk, 0, ctx.stream, AFEM_EL_ARGS);
+  else
+    hipLaunchKernelGGL((k_assemble_elast_tri<false, 2>), grid, blk, 0, ctx.stream, AFEM_EL_ARGS);
 #undef AFEM_EL_ARGS
   AFEM_LAUNCHED();
   b.last_kernel = AFEM_KERNEL_ELAST2;

@@ -547,6 +547,27 @@ int afem_bsr_assemble_elasticity_p1_ex(afem_bsr* b, double lambda, double mu2, d
   API_END
 }
 
+int afem_bsr_assemble_elastodynamics_p1(afem_bsr* b, const double c[11], const double* body_force, const double* u,
+                                        const double* v, const double* a, const uint8_t* fixed, double* rhs,
+                                        int rhs_mode)
+{
+  API_BEGIN
+  AFEM_RANGE("afem: elastodynamics step assembly (TRIA3)");
+  NOT_NULL(b);
+  AFEM_REQUIRE(b->has_sparsity, AFEM_ERR_STATE, "assembleBilinear called before computeSparsity");
+  AFEM_REQUIRE(b->mesh->nv == 3 && b->nb_dof == 2, AFEM_ERR_NOT_IMPL,
+               "the fused elastodynamics step is implemented for NB_DOF = 2 on triangles");
+  NOT_NULL(c);
+  NOT_NULL(u);
+  NOT_NULL(v);
+  NOT_NULL(a);
+  NOT_NULL(rhs);
+  AFEM_REQUIRE(rhs_mode == AFEM_RHS_ADD || rhs_mode == AFEM_RHS_SET, AFEM_ERR_ARG, "unknown rhs_mode");
+  b->mesh->ctx->set_device();
+  assemble_elastodynamics_tri(*b, c, body_force, u, v, a, fixed, rhs, rhs_mode == AFEM_RHS_ADD ? 1 : 0);
+  API_END
+}
+
 int afem_bsr_reset_values(afem_bsr* b)
 {
   API_BEGIN
@@ -1455,7 +1476,10 @@ int afem_elastodynamics_set_solver_options(afem_elastodynamics* h, const afem_so
   API_BEGIN
   NOT_NULL(h);
   NOT_NULL(o);
-  AFEM_REQUIRE(o->method != AFEM_SOLVER_DIRECT, AFEM_ERR_NOT_IMPL, "elastodynamics solves with the Jacobi-PCG");
+  const bool tri = h->d->nb == 2;  // the 2D loop keeps the direct branch for small systems
+  AFEM_REQUIRE(tri || o->method != AFEM_SOLVER_DIRECT, AFEM_ERR_NOT_IMPL, "elastodynamics solves with the Jacobi-PCG");
+  AFEM_REQUIRE(!tri || (o->precond_block != 3 && !o->multigrid && !o->amg), AFEM_ERR_NOT_IMPL,
+               "2D elastodynamics: the Jacobi-PCG or the direct solver (no block-3, multigrid or AMG preconditioner)");
   AFEM_REQUIRE(o->max_iter >= 0 && o->rtol >= 0 && o->atol >= 0, AFEM_ERR_ARG, "bad solver options");
   AFEM_REQUIRE(o->precond_block == 0 || o->precond_block == 1 || o->precond_block == 3, AFEM_ERR_ARG,
                "precond_block must be 0, 1 or 3");
@@ -1468,7 +1492,7 @@ int afem_elastodynamics_set_solver_options(afem_elastodynamics* h, const afem_so
   h->d->ls.mg.reset();
   h->d->ls.amg.reset();
   h->d->ls.opts = *o;
-  h->d->ls.opts.method = AFEM_SOLVER_PCG;
+  if (!tri) h->d->ls.opts.method = AFEM_SOLVER_PCG;
   API_END
 }
 
@@ -1487,6 +1511,41 @@ int afem_elastodynamics_set_dirichlet(afem_elastodynamics* h, const int32_t* dof
   API_BEGIN
   NOT_NULL(h);
   dyn_set_dirichlet(h->d, dofs, values, n, mem);
+  API_END
+}
+
+int afem_elastodynamics_set_lame(afem_elastodynamics* h, double lambda, double mu)
+{
+  API_BEGIN
+  NOT_NULL(h);
+  dyn_set_lame(h->d, lambda, mu);
+  API_END
+}
+
+int afem_elastodynamics_set_dirichlet_vectorial(afem_elastodynamics* h, const int32_t* nodes, int64_t n,
+                                                const double values[2], unsigned component_mask, int method, int mem)
+{
+  API_BEGIN
+  NOT_NULL(h);
+  dyn_set_dirichlet_vectorial(h->d, nodes, n, values, component_mask, method, mem);
+  API_END
+}
+
+int afem_elastodynamics_set_traction(afem_elastodynamics* h, const int32_t* face_nodes, int64_t n_faces,
+                                     const double t[2], unsigned component_mask, int mem)
+{
+  API_BEGIN
+  NOT_NULL(h);
+  dyn_set_traction(h->d, face_nodes, n_faces, t, component_mask, mem);
+  API_END
+}
+
+int afem_elastodynamics_set_traction_table(afem_elastodynamics* h, int traction_index, const double* times,
+                                           const double* values, int64_t n)
+{
+  API_BEGIN
+  NOT_NULL(h);
+  dyn_set_traction_table(h->d, traction_index, times, values, n);
   API_END
 }
 
@@ -1518,7 +1577,7 @@ int afem_elastodynamics_operators(afem_elastodynamics* h, afem_csr_view* lhs, co
     lhs->n_block_rows = d->K.s.n_rows;
     lhs->n_block_cols = d->mesh->n_nodes;
     lhs->nnz_blocks = d->K.s.nnz;
-    lhs->block_size = 3;
+    lhs->block_size = d->nb;
     lhs->ordered_per_block = d->K.order_per_block ? 1 : 0;
     lhs->rows = d->K.s.row_ptr.p;
     lhs->columns = d->K.s.cols.p;

@@ -48,7 +48,30 @@ __global__ void k_scatter_vals(int64_t n, const int32_t* __restrict__ ids, const
     x[ids[i]] = vals[i];
 }
 
+// Traction of the 2D elastodynamics loop (modules/elastodynamics/FemModule.cc:
+// 880-967): node nodes[i] carries w[i] = sum of |e| / 2 over the group's edges
+// at it; rhs[2 node + c] += t_c w[i] for the components of `mask`, unless the
+// DoF is flagged.  Every node is listed once: one writer per DoF.
+__global__ void k_traction2(int64_t n, const int32_t* __restrict__ nodes, const double* __restrict__ w, double t0,
+                            double t1, unsigned mask, const uint8_t* __restrict__ fixed, double* __restrict__ rhs)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t d = 2 * (int64_t)nodes[i];
+  if ((mask & 1u) && !fixed[d]) rhs[d] += t0 * w[i];
+  if ((mask & 2u) && !fixed[d + 1]) rhs[d + 1] += t1 * w[i];
+}
+
 }  // namespace
+
+void traction2_add(Ctx& ctx, int64_t n, const int32_t* nodes, const double* w, const double t[2], unsigned mask,
+                   const uint8_t* fixed, double* rhs)
+{
+  if (n <= 0 || !(mask & 3u)) return;
+  hipLaunchKernelGGL(k_traction2, dim3(grid_for(n, 256)), dim3(256), 0, ctx.stream, n, nodes, w, t[0], t[1], mask,
+                     fixed, rhs);
+  AFEM_LAUNCHED();
+}
 
 void vec_scatter(Ctx& ctx, int64_t n, const int32_t* ids, const double* vals, double* x)
 {

@@ -16,6 +16,16 @@
 // c0 M + K(c1, c2) and the RHS adds K(lambda = 1) (-c5 U + c7 V + c8 A) +
 // K(2 mu = 1) (-c6 U + c9 V + c10 A) (:842-862) -- two more operators on the
 // same structure, assembled once.
+//
+// The module's own case, 2D TRIA3 with block 2, runs through the same handle
+// (nb = 2, dyn_create_tri / dyn_step_tri): one fused kernel per step writes
+// the LHS and the complete RHS from U, V, A (assemble_elastodynamics_tri), so
+// that path keeps no M / K_lambda / K_mu and runs no SpMV or lincomb for the
+// RHS; tractions (:880-967, constant or a CaseTable), the vectorial Dirichlet
+// blocks (Penalty, RowElimination, RowColumnElimination; NULL components), the
+// re-imposition of the constrained values after the solve (:1416-1417) and
+// the Newmark update follow.  One subdomain.
+#include <algorithm>
 #include <cmath>
 #include <map>
 #include <vector>
@@ -121,11 +131,280 @@ void dyn_coefficients(Elastodynamics* d)
   }
 }
 
+namespace {
+Elastodynamics* dyn_create_tri(Mesh* mesh, Comm* comm, const afem_newmark_params* prm, const int32_t* fixed_nodes,
+                               int64_t n_fixed, int mem)
+{
+  AFEM_REQUIRE(prm->dt > 0 && prm->E > 0 && prm->nu > -1.0 && prm->nu < 0.5 && prm->rho >= 0, AFEM_ERR_ARG,
+               "elastodynamics: bad material or time step");
+  AFEM_REQUIRE(n_fixed == 0 || fixed_nodes, AFEM_ERR_ARG, "fixed_nodes is NULL");
+  AFEM_REQUIRE(prm->scheme == 0 || prm->scheme == 1, AFEM_ERR_ARG,
+               "elastodynamics: scheme 0 (Newmark-beta) or 1 (generalized-alpha)");
+  AFEM_REQUIRE(!comm || comm_nranks(comm) == 1, AFEM_ERR_NOT_IMPL,
+               "2D elastodynamics runs on one subdomain (a communicator of more than one rank)");
+  AFEM_REQUIRE(mesh->n_own == mesh->n_nodes, AFEM_ERR_NOT_IMPL,
+               "2D elastodynamics runs on one subdomain (the mesh has ghost nodes)");
+  mesh->ctx->set_device();
+  auto* d = new Elastodynamics();
+  try {
+    Ctx& ctx = *mesh->ctx;
+    d->mesh = mesh;
+    d->ctx = &ctx;
+    d->comm = comm;
+    d->p = *prm;
+    d->nb = 2;
+    if (!(d->p.penalty > 0)) d->p.penalty = 1.0e30;
+    d->mu2 = (prm->E / (2 * (1 + prm->nu))) * 2;  // FemModule.cc:239-240; afem_elastodynamics_set_lame: :242-246
+    d->lambda = prm->E * prm->nu / ((1 + prm->nu) * (1 - 2 * prm->nu));
+    dyn_coefficients(d);
+    d->damped = prm->etak != 0.0 || (prm->scheme == 1 && prm->alpf != 0.0);
+    d->t = prm->dt;
+    d->n = 2 * mesh->n_own;
+    d->n_cols = 2 * mesh->n_nodes;
+    d->K.mesh = mesh;
+    d->K.nb_dof = 2;
+    d->K.order_per_block = false;  // CSR row order: the values are the linear system's matrix
+    build_structure(*mesh, d->K.s, 2);
+    d->K.values.alloc((size_t)d->K.s.nnz * 4);
+    AFEM_HIP(hipMemsetAsync(d->K.values.p, 0, d->K.values.bytes(), ctx.stream));
+    d->K.has_sparsity = true;
+    bsr_expand_scalar(d->K, nullptr);
+    init_ls(d->ls, &ctx, d->n, d->n_cols);
+    LinearSystem& l = d->ls;
+    l.has_csr = true;
+    l.csr_n = d->n;
+    l.csr_nnz = d->K.s.nnz * 4;
+    l.csr_rows = d->K.csr_rows.p;
+    l.csr_diag = nullptr;
+    l.csr_cols = d->K.csr_cols.p;
+    l.csr_vals = d->K.values.p;
+    l.blk_k = 2;
+    l.blk_n = d->K.s.n_rows;
+    l.blk_rows = d->K.s.row_ptr.p;
+    l.blk_cols = d->K.s.cols.p;
+    for (auto* b : { &d->U, &d->V, &d->A }) {
+      b->alloc(d->n_cols);
+      AFEM_HIP(hipMemsetAsync(b->p, 0, b->bytes(), ctx.stream));
+    }
+    d->fixed2.alloc(d->n);
+    AFEM_HIP(hipMemsetAsync(d->fixed2.p, 0, d->fixed2.bytes(), ctx.stream));
+    ctx.sync();
+    if (n_fixed) {  // the clamped nodes of the 3D entry: both components 0, by penalty
+      const double zero[2] = { 0.0, 0.0 };
+      dyn_set_dirichlet_vectorial(d, fixed_nodes, n_fixed, zero, 3u, AFEM_DIRICHLET_PENALTY, mem);
+    }
+  }
+  catch (...) {
+    delete d;
+    throw;
+  }
+  return d;
+}
+
+void dyn_step_tri(Elastodynamics* d, afem_solve_stats* st)
+{
+  Ctx& ctx = *d->ctx;
+  ctx.set_device();
+  const bool prof = d->profile;
+  auto mark = [&](int i) {
+    if (prof) AFEM_HIP(hipEventRecord(d->ev[i], ctx.stream));
+  };
+  const int32_t prof_opt = d->ls.opts.profile_comm;
+  if (prof) d->ls.opts.profile_comm = 1;
+  mark(0);
+  // LHS c0 M + K(c1, c2) and the whole RHS of :645-867 in one pass (set mode)
+  const double f[2] = { d->p.body_force[0], d->p.body_force[1] };
+  assemble_elastodynamics_tri(d->K, d->c, f, d->U.p, d->V.p, d->A.p, d->fixed2.p, d->ls.rhs.p, 0);
+  mark(1);
+  // tractions t_i |e| / 2 per face node on the unfixed DoFs (:880-967), at the step's time for a table
+  for (const auto& tr : d->trac2) {
+    double t[2] = { tr.t[0], tr.t[1] };
+    if (!tr.times.empty()) table_interp2(tr.times, tr.values, d->t, t);
+    traction2_add(ctx, (int64_t)tr.nodes.n, tr.nodes.p, tr.w.p, t, tr.mask, d->fixed2.p, d->ls.rhs.p);
+  }
+  mark(2);
+  // the deck's Dirichlet blocks in their order: later ones override earlier ones per DoF
+  for (const auto& dc : d->dir2)
+    ls_set_vectorial(d->ls, 2, dc.nodes.p, (int64_t)dc.nodes.n, AFEM_MEM_DEVICE, d->dir_method, dc.v, dc.mask,
+                     d->p.penalty);
+  // warm start from the Newmark predictor, as in 3D
+  vec_lincomb(ctx, d->n, 1.0, d->U.p, d->p.dt, d->V.p, d->p.dt * d->p.dt * (0.5 - d->beta), d->A.p, d->ls.sol.p);
+  d->ls.opts.initial_guess = 1;
+  mark(3);
+  ls_solve(d->ls, &d->last);
+  d->ls.opts.profile_comm = prof_opt;
+  mark(4);
+  // the constrained values re-imposed on the solution (_solve, :1416-1417)
+  if (d->imp_ids.n) vec_scatter(ctx, (int64_t)d->imp_ids.n, d->imp_ids.p, d->imp_vals.p, d->ls.sol.p);
+  newmark_update(ctx, d->n, d->p.dt, d->beta, d->gamma, d->ls.sol.p, d->U.p, d->V.p, d->A.p);
+  mark(5);
+  ctx.sync();
+  d->t += d->p.dt;  // _updateTime, :189
+  if (prof) {
+    float ms[5] = {};
+    for (int i = 0; i < 5; ++i) AFEM_HIP(hipEventElapsedTime(&ms[i], d->ev[i], d->ev[i + 1]));
+    float tot = 0.f;
+    AFEM_HIP(hipEventElapsedTime(&tot, d->ev[0], d->ev[5]));
+    afem_step_timing& t = d->timing;
+    t.assemble_ms = ms[0];
+    t.rhs_ms = ms[1];
+    t.bc_ms = ms[2];
+    t.solve_ms = ms[3];
+    t.precond_ms = d->last.precond_ms;
+    t.update_ms = ms[4];
+    t.total_ms = tot;
+    t.iterations = d->last.iterations;
+  }
+  if (st) *st = d->last;
+}
+
+template <class T>
+std::vector<T> to_host(Ctx& ctx, const T* p, int64_t n, int mem)
+{
+  std::vector<T> h(n);
+  if (n) {
+    AFEM_HIP(hipMemcpyAsync(h.data(), p, n * sizeof(T), mem == AFEM_MEM_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost,
+                            ctx.stream));
+    ctx.sync();
+  }
+  return h;
+}
+
+template <class T>
+void upload(Ctx& ctx, DevBuf<T>& b, const std::vector<T>& h)
+{
+  b.alloc(h.size());
+  if (!h.empty()) AFEM_HIP(hipMemcpyAsync(b.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, ctx.stream));
+  ctx.sync();
+}
+}  // namespace
+
+void table_interp2(const std::vector<double>& times, const std::vector<double>& values, double t, double out[2])
+{
+  const size_t n = times.size();
+  if (t <= times.front() || n == 1) {
+    out[0] = values[0];
+    out[1] = values[1];
+    return;
+  }
+  if (t >= times.back()) {
+    out[0] = values[2 * n - 2];
+    out[1] = values[2 * n - 1];
+    return;
+  }
+  const size_t k = std::upper_bound(times.begin(), times.end(), t) - times.begin();  // times[k-1] <= t < times[k]
+  const double w = (t - times[k - 1]) / (times[k] - times[k - 1]);
+  for (int i = 0; i < 2; ++i) out[i] = values[2 * (k - 1) + i] + w * (values[2 * k + i] - values[2 * (k - 1) + i]);
+}
+
+void dyn_set_lame(Elastodynamics* d, double lambda, double mu)
+{
+  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, "afem_elastodynamics_set_lame: the 2D loop's entry");
+  AFEM_REQUIRE(mu > 0 && lambda + mu > 0, AFEM_ERR_ARG, "afem_elastodynamics_set_lame: bad Lame parameters");
+  d->lambda = lambda;
+  d->mu2 = 2 * mu;
+  dyn_coefficients(d);
+}
+
+void dyn_set_dirichlet_vectorial(Elastodynamics* d, const int32_t* nodes, int64_t n, const double values[2],
+                                 unsigned mask, int method, int mem)
+{
+  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, "afem_elastodynamics_set_dirichlet_vectorial: the 2D loop's entry");
+  AFEM_REQUIRE(n >= 0 && (n == 0 || nodes) && values, AFEM_ERR_ARG,
+               "afem_elastodynamics_set_dirichlet_vectorial: bad node list or values");
+  AFEM_REQUIRE(method == AFEM_DIRICHLET_PENALTY || method == AFEM_DIRICHLET_ROW_ELIMINATION ||
+                   method == AFEM_DIRICHLET_ROW_COLUMN_ELIMINATION,
+               AFEM_ERR_NOT_IMPL,
+               "enforce-Dirichlet-method: Penalty, RowElimination or RowColumnElimination (WeakPenalty is not "
+               "implemented)");
+  AFEM_REQUIRE(d->dir_method < 0 || d->dir_method == method, AFEM_ERR_ARG,
+               "one enforce-Dirichlet-method for all conditions of a run");
+  mask &= 3u;
+  if (n == 0 || !mask) return;
+  Ctx& ctx = *d->ctx;
+  ctx.set_device();
+  const std::vector<int32_t> hn = to_host(ctx, nodes, n, mem);
+  std::vector<int32_t> own;
+  for (int32_t v : hn) {
+    AFEM_REQUIRE(v >= 0 && v < d->mesh->n_nodes, AFEM_ERR_ARG, "Dirichlet node id out of range");
+    if (v < d->mesh->n_own) own.push_back(v);
+  }
+  d->dir_method = method;
+  Elastodynamics::Dirichlet2 dc;
+  upload(ctx, dc.nodes, own);
+  dc.mask = mask;
+  for (int i = 0; i < 2; ++i) dc.v[i] = (mask >> i) & 1u ? values[i] : 0.0;
+  for (int32_t v : own)
+    for (int i = 0; i < 2; ++i)
+      if ((mask >> i) & 1u) d->dir_dofs[2 * v + i] = values[i];
+  d->dir2.push_back(std::move(dc));
+  // the flags of the kernel's and the tractions' guards, and the list re-imposed after the solve
+  std::vector<uint8_t> flags(d->n, 0);
+  std::vector<int32_t> ids;
+  std::vector<double> vals;
+  for (const auto& kv : d->dir_dofs) {
+    flags[kv.first] = 1;
+    ids.push_back(kv.first);
+    vals.push_back(kv.second);
+  }
+  upload(ctx, d->fixed2, flags);
+  upload(ctx, d->imp_ids, ids);
+  upload(ctx, d->imp_vals, vals);
+}
+
+void dyn_set_traction(Elastodynamics* d, const int32_t* face_nodes, int64_t n_faces, const double t[2], unsigned mask,
+                      int mem)
+{
+  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, "afem_elastodynamics_set_traction: the 2D loop's entry");
+  AFEM_REQUIRE(n_faces >= 0 && (n_faces == 0 || face_nodes) && t, AFEM_ERR_ARG,
+               "afem_elastodynamics_set_traction: bad face list or traction");
+  Ctx& ctx = *d->ctx;
+  ctx.set_device();
+  const std::vector<int32_t> fn = to_host(ctx, face_nodes, 2 * n_faces, mem);
+  const std::vector<double> xyz = to_host(ctx, d->mesh->coords.p, 3 * d->mesh->n_nodes, AFEM_MEM_DEVICE);
+  std::map<int32_t, double> w;  // node -> sum of |e| / 2, faces in their order
+  for (int64_t f = 0; f < n_faces; ++f) {
+    const int32_t a = fn[2 * f], b = fn[2 * f + 1];
+    AFEM_REQUIRE(a >= 0 && a < d->mesh->n_nodes && b >= 0 && b < d->mesh->n_nodes, AFEM_ERR_ARG,
+                 "traction face node id out of range");
+    const double len = std::hypot(xyz[3 * a] - xyz[3 * b], xyz[3 * a + 1] - xyz[3 * b + 1]);
+    for (int32_t v : { a, b })
+      if (v < d->mesh->n_own) w[v] += len / 2.;
+  }
+  std::vector<int32_t> nodes;
+  std::vector<double> ws;
+  for (const auto& kv : w) {
+    nodes.push_back(kv.first);
+    ws.push_back(kv.second);
+  }
+  Elastodynamics::Traction2 tr;
+  upload(ctx, tr.nodes, nodes);
+  upload(ctx, tr.w, ws);
+  tr.mask = mask & 3u;
+  for (int i = 0; i < 2; ++i) tr.t[i] = (tr.mask >> i) & 1u ? t[i] : 0.0;
+  d->trac2.push_back(std::move(tr));
+}
+
+void dyn_set_traction_table(Elastodynamics* d, int index, const double* times, const double* values, int64_t n)
+{
+  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, "afem_elastodynamics_set_traction_table: the 2D loop's entry");
+  AFEM_REQUIRE(index >= 0 && index < (int)d->trac2.size(), AFEM_ERR_ARG,
+               "afem_elastodynamics_set_traction_table: no such traction");
+  AFEM_REQUIRE(n >= 1 && times && values, AFEM_ERR_ARG, "afem_elastodynamics_set_traction_table: empty table");
+  for (int64_t i = 1; i < n; ++i)
+    AFEM_REQUIRE(times[i] > times[i - 1], AFEM_ERR_ARG, "afem_elastodynamics_set_traction_table: times must increase");
+  auto& tr = d->trac2[index];
+  tr.times.assign(times, times + n);
+  tr.values.assign(values, values + 2 * n);
+}
+
 Elastodynamics* dyn_create(Mesh* mesh, Comm* comm, const afem_newmark_params* prm, const int32_t* fixed_nodes,
                            int64_t n_fixed, int mem)
 {
+  if (mesh->nv == 3 && mesh->dim == 2) return dyn_create_tri(mesh, comm, prm, fixed_nodes, n_fixed, mem);
   {
-    AFEM_REQUIRE(mesh->nv == 4 && mesh->dim == 3, AFEM_ERR_NOT_IMPL, "elastodynamics needs a tetrahedral mesh");
+    AFEM_REQUIRE(mesh->nv == 4 && mesh->dim == 3, AFEM_ERR_NOT_IMPL,
+                 "elastodynamics needs a tetrahedral (3D) or a triangle (2D) mesh");
     AFEM_REQUIRE(prm->dt > 0 && prm->E > 0 && prm->nu > -1.0 && prm->nu < 0.5 && prm->rho >= 0, AFEM_ERR_ARG,
                  "elastodynamics: bad material or time step");
     AFEM_REQUIRE(n_fixed == 0 || fixed_nodes, AFEM_ERR_ARG, "fixed_nodes is NULL");
@@ -249,6 +528,10 @@ Elastodynamics* dyn_create(Mesh* mesh, Comm* comm, const afem_newmark_params* pr
 
 void dyn_step(Elastodynamics* d, afem_solve_stats* st)
 {
+  if (d->nb == 2) {
+    dyn_step_tri(d, st);
+    return;
+  }
   {
     Ctx& ctx = *d->ctx;
     ctx.set_device();
@@ -319,6 +602,8 @@ void dyn_set_dirichlet(Elastodynamics* d, const int32_t* dofs, const double* val
 {
   AFEM_REQUIRE(n == 0 || (dofs && values), AFEM_ERR_ARG, "afem_elastodynamics_set_dirichlet: dofs / values is NULL");
   AFEM_REQUIRE(n >= 0, AFEM_ERR_ARG, "afem_elastodynamics_set_dirichlet: negative count");
+  AFEM_REQUIRE(d->nb == 3, AFEM_ERR_NOT_IMPL,
+               "afem_elastodynamics_set_dirichlet is the 3D loop's entry (2D: afem_elastodynamics_set_dirichlet_vectorial)");
   Ctx& ctx = *d->ctx;
   ctx.set_device();
   std::vector<int32_t> hd(n);

@@ -226,6 +226,27 @@ int afem_bsr_assemble_elasticity_p1(afem_bsr* bsr, double lambda, double mu2);
  * combinations: AFEM_ERR_NOT_IMPL. */
 int afem_bsr_assemble_elasticity_p1_ex(afem_bsr* bsr, double lambda, double mu2, double mass_coef,
                                        const double* body_force, double* rhs, int rhs_mode);
+/* The fused step of the 2D elastodynamics module (modules/elastodynamics/
+ * FemModule.cc, TRIA3, block 2): in one pass over the owned rows
+ *   values = c[0] M + K(lambda = c[1], 2 mu = c[2])   -- exactly the values of
+ *            afem_bsr_assemble_elasticity_p1_ex(c[1], c[2], c[0]), bit for bit --
+ *   rhs[2r+i] = f_i (sum |K|) / 3 + sum over the row's triangles and their nodes b of
+ *               m_rb Wm_b,i + Klambda_(r,i),(b,.) Wl_b + Kmu_(r,i),(b,.) Wu_b,
+ *   Wm = c0 U + c3 V + c4 A,  Wl = -c5 U + c7 V + c8 A,  Wu = -c6 U + c9 V + c10 A
+ * (the cell loop of FemModule.cc:671-867 regrouped by linearity; c = the
+ * module's c0 .. c10, :255-290; m_rb = |K|/6 or |K|/12; Klambda / Kmu the
+ * lambda = 1 / 2 mu = 1 parts of the element matrix).  u, v, a: 2 doubles per
+ * LOCAL node (ghosts included, supplied by the caller); body_force: 2 doubles
+ * (host) or NULL; fixed: one byte per owned DoF or NULL -- a flagged DoF gets
+ * 0 (AFEM_RHS_SET) or is left untouched (AFEM_RHS_ADD), the module's
+ * m_u1_fixed / m_u2_fixed guards; rhs: 2 per owned node.  u, v, a, fixed, rhs
+ * are device pointers.  With c5 .. c10 all zero (undamped Newmark-beta) the
+ * instance without the stiffness terms runs.  No stored M / K operators, no
+ * SpMV, no atomics on global memory; bitwise reproducible.  Other (cell,
+ * NB_DOF) combinations: AFEM_ERR_NOT_IMPL. */
+int afem_bsr_assemble_elastodynamics_p1(afem_bsr* bsr, const double c[11], const double* body_force, const double* u,
+                                        const double* v, const double* a, const uint8_t* fixed, double* rhs,
+                                        int rhs_mode);
 int afem_bsr_reset_values(afem_bsr* bsr);                       /* resetMatrixValues */
 int afem_bsr_set_value(afem_bsr* bsr, int32_t row, int32_t col, double v); /* BSRMatrix::setValue */
 int afem_bsr_get_value(afem_bsr* bsr, int32_t row, int32_t col, double* v); /* BSRMatrix::getValue */
@@ -672,8 +693,9 @@ typedef struct afem_newmark_params {
   int32_t scheme;
   int32_t reserved0;
 } afem_newmark_params;
-/* fixed_nodes: local node ids (in `mem`) whose 3 DoFs are clamped to 0; comm
- * may be NULL (one subdomain). */
+/* fixed_nodes: local node ids (in `mem`) whose DoFs are clamped to 0; comm
+ * may be NULL (one subdomain).  A tetrahedral mesh gives the 3D loop, a
+ * triangle mesh the 2D one (below). */
 int afem_elastodynamics_create(afem_mesh* mesh, afem_comm* comm, const afem_newmark_params* params,
                                const int32_t* fixed_nodes, int64_t n_fixed, int mem, afem_elastodynamics** out);
 int afem_elastodynamics_set_solver_options(afem_elastodynamics* dyn, const afem_solver_opts* opts);
@@ -688,11 +710,50 @@ int afem_elastodynamics_step(afem_elastodynamics* dyn, afem_solve_stats* stats);
  * stay clamped. */
 int afem_elastodynamics_set_dirichlet(afem_elastodynamics* dyn, const int32_t* dofs, const double* values, int64_t n,
                                       int mem);
+/* ---- the 2D loop (a triangle mesh given to afem_elastodynamics_create): the
+ * module modules/elastodynamics itself, block 2, one subdomain (a communicator
+ * of more than one rank or a mesh with ghosts: AFEM_ERR_NOT_IMPL).  Per step:
+ * afem_bsr_assemble_elastodynamics_p1 in set mode (LHS and complete RHS, no
+ * stored operators), the tractions, the Dirichlet blocks through the
+ * afem_ls_dirichlet_vectorial machinery, the solve (Jacobi-PCG, or the direct
+ * solver when the options ask for it / AFEM_SOLVER_AUTO below 500 rows; warm
+ * started from the Newmark predictor), the constrained values re-imposed on
+ * the solution (_solve, FemModule.cc:1416-1417), the Newmark update.  State
+ * arrays: 2 per node.  fixed_nodes of create: both components 0 by penalty.
+ * afem_elastodynamics_set_dirichlet and the multigrid / AMG / block-3
+ * preconditioners are the 3D loop's (AFEM_ERR_NOT_IMPL here). */
+/* Lame parameters given directly, as the decks do (FemModule.cc:242-246);
+ * replaces the values derived from E and nu. */
+int afem_elastodynamics_set_lame(afem_elastodynamics* dyn, double lambda, double mu);
+/* One dirichlet-boundary-condition / dirichlet-point-condition block: the
+ * group's nodes, values[2] and the components present (bit i of
+ * component_mask; a cleared bit is the deck's missing u_i).  method:
+ * AFEM_DIRICHLET_PENALTY (with afem_newmark_params.penalty),
+ * _ROW_ELIMINATION or _ROW_COLUMN_ELIMINATION, the same for all blocks
+ * (WeakPenalty: AFEM_ERR_NOT_IMPL).  Blocks accumulate; a later block
+ * overrides an earlier one per DoF.  The stated value is imposed with every
+ * method (the reference's RowColumnElimination branch takes the previous
+ * displacement for u2, FemModule.cc:619). */
+int afem_elastodynamics_set_dirichlet_vectorial(afem_elastodynamics* dyn, const int32_t* nodes, int64_t n,
+                                                const double values[2], unsigned component_mask, int method, int mem);
+/* One traction-boundary-condition block: rhs[2 v + i] += t_i |e| / 2 for both
+ * nodes v of every listed edge (face_nodes[2 n_faces], local ids), owned and
+ * not constrained DoFs only (FemModule.cc:880-967); component_mask as above.
+ * Blocks accumulate; the k-th call has traction_index k. */
+int afem_elastodynamics_set_traction(afem_elastodynamics* dyn, const int32_t* face_nodes, int64_t n_faces,
+                                     const double t[2], unsigned component_mask, int mem);
+/* traction-input-file: the traction of block traction_index (both components)
+ * becomes the piecewise-linear interpolation of (times[n], values[n][2], host)
+ * at the step's time, constant outside the table (CaseTable::CurveLinear,
+ * femutils/FemUtils.cc:208); the time starts at dt and advances by dt after
+ * each step (FemModule.cc:175, :189). */
+int afem_elastodynamics_set_traction_table(afem_elastodynamics* dyn, int traction_index, const double* times,
+                                           const double* values, int64_t n);
 /* Changes dt from the next step on (passmo shortens the step that would
  * overshoot the final time, modules/passmo/ElastodynamicModule.cc:525-530);
  * the Newmark coefficients follow and a reused multigrid hierarchy is rebuilt. */
 int afem_elastodynamics_set_time_step(afem_elastodynamics* dyn, double dt);
-/* device arrays of 3*n_own_nodes doubles (DoF lid = 3 node + i) */
+/* device arrays of dim*n_own_nodes doubles (DoF lid = dim node + i) */
 int afem_elastodynamics_state(afem_elastodynamics* dyn, double** u, double** v, double** a);
 /* The step's operators on the device, for checks and callers that post-process
  * (passmo assembles the same c0 M + K on the CPU, ElastodynamicModule.cc:
@@ -709,8 +770,8 @@ int afem_elastodynamics_operators(afem_elastodynamics* dyn, afem_csr_view* lhs, 
  * preconditioner applications (afem_solve_stats.precond_ms). */
 int afem_elastodynamics_profile(afem_elastodynamics* dyn, int on);
 typedef struct afem_step_timing {
-  double assemble_ms;  /* fused block-3 re-assembly of c0 M + K + body force */
-  double rhs_ms;       /* RHS operators: lincombs + mass (and damping) SpMVs */
+  double assemble_ms;  /* fused block-3 re-assembly of c0 M + K + body force (2D: the fused step kernel, LHS + RHS) */
+  double rhs_ms;       /* RHS operators: lincombs + mass (and damping) SpMVs (2D: the tractions) */
   double bc_ms;        /* penalty lists + the Newmark predictor (the warm start) */
   double solve_ms;     /* the PCG (setup of a new multigrid hierarchy included) */
   double precond_ms;   /* part of solve_ms: the preconditioner applications */
