@@ -121,6 +121,12 @@ class PrecondLevel(ctypes.Structure):
                 ("coarse_sweeps", ctypes.c_int32), ("scale", ctypes.c_double)]
 
 
+class SpmvPlanInfo(ctypes.Structure):
+    _fields_ = [("rpb", ctypes.c_int32), ("wide", ctypes.c_int32), ("unroll", ctypes.c_int32),
+                ("bs", ctypes.c_int32), ("blk_k", ctypes.c_int32), ("pat_len", ctypes.c_int32),
+                ("max_seg", ctypes.c_int64), ("nblocks", ctypes.c_int64), ("pat_rows", ctypes.c_int64)]
+
+
 class StepTiming(ctypes.Structure):
     _fields_ = [("assemble_ms", ctypes.c_double), ("rhs_ms", ctypes.c_double), ("bc_ms", ctypes.c_double),
                 ("solve_ms", ctypes.c_double), ("precond_ms", ctypes.c_double), ("update_ms", ctypes.c_double),
@@ -231,6 +237,7 @@ SIGNATURES = {
     "afem_ls_precond_level_info": [P, I32, ctypes.POINTER(PrecondLevel)],
     "afem_ls_precond_level_copy": [P, I32, P, P, P, P, P, P, P, P, P],
     "afem_ls_spmv": [P, P, P],
+    "afem_ls_spmv_plan_info": [P, ctypes.POINTER(SpmvPlanInfo)],
     "afem_ls_destroy": [P],
     "afem_comm_unique_id": [P],
     "afem_comm_create": [P, P, INT, INT, PP],

@@ -421,6 +421,25 @@ class DoFLinearSystem:
         # caller's own array, so its later edits are seen
         self._host_view = (rows, rnc, columns, values)
 
+    def setCSRValuesDevice(self, rows_host, cols_dptr: int, vals_dptr: int, nb_row: int, nb_nz: int):
+        """setCSRValues for a device view: `rows_host` (row starts, no
+        sentinel) is a host array, columns and values are device addresses that
+        the linear system uses in place until solve (the caller keeps them
+        alive; the boundary conditions are written into the values)."""
+        self._check_init()
+        rows = np.ascontiguousarray(rows_host, dtype=np.int32)
+        if rows.shape[0] != nb_row:
+            raise ValueError("rows_host must hold nb_row entries")
+        # the C entry reads `rows` with the view's memory kind: a device copy for the call
+        rows_d = self.ctx.malloc(max(rows.nbytes, 4))
+        try:
+            self.ctx.to_device(rows_d, rows)
+            call("afem_ls_set_csr_values", self.impl, ctypes.c_void_p(rows_d), None, ctypes.c_void_p(cols_dptr),
+                 ctypes.c_void_p(vals_dptr), nb_row, nb_nz, C.AFEM_MEM_DEVICE)
+        finally:
+            self.ctx.free(rows_d)
+        self._host_view = None
+
     def hasSetCSRValues(self) -> bool:
         self._check_init()
         h = ctypes.c_int()
@@ -616,6 +635,15 @@ class DoFLinearSystem:
 
     def spmv(self, x_dptr: int, y_dptr: int):
         call("afem_ls_spmv", self.impl, ctypes.c_void_p(x_dptr), ctypes.c_void_p(y_dptr))
+
+    def spmvPlanInfo(self) -> dict:
+        """Diagnostic: the SpMV plan that spmv() / solve() choose for the
+        current matrix under the variants set now (afem_spmv_plan_info)."""
+        self._check_init()
+        o = C.SpmvPlanInfo()
+        call("afem_ls_spmv_plan_info", self.impl, ctypes.byref(o))
+        return dict(rpb=o.rpb, wide=bool(o.wide), unroll=bool(o.unroll), bs=o.bs, blk_k=o.blk_k, pat_len=o.pat_len,
+                    max_seg=o.max_seg, nblocks=o.nblocks, pat_rows=o.pat_rows)
 
     def clearValues(self):
         self._check_init()

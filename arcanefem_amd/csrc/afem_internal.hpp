@@ -588,6 +588,7 @@ struct PrecondLevelView {
 bool mg_level_view(const LinearSystem& ls, int level, PrecondLevelView& out);
 bool amg_level_view(const LinearSystem& ls, int level, PrecondLevelView& out);
 void ls_spmv(LinearSystem& ls, const double* x, double* y);
+void ls_spmv_plan_info(LinearSystem& ls, afem_spmv_plan_info* out);
 void ls_spmv_planned(LinearSystem& ls, const double* x, double* y);
 // algebraic multigrid preconditioner (amg.hip)
 bool amg_available(const LinearSystem& ls);

@@ -1428,6 +1428,16 @@ int afem_ls_spmv(afem_ls* ls, const double* x, double* y)
   API_END
 }
 
+int afem_ls_spmv_plan_info(afem_ls* ls, afem_spmv_plan_info* out)
+{
+  API_BEGIN
+  NOT_NULL(ls);
+  NOT_NULL(out);
+  ls->ctx->set_device();
+  ls_spmv_plan_info(*ls, out);
+  API_END
+}
+
 int afem_vec_lincomb(afem_ctx* ctx, int64_t n, double a, const double* x, double b, const double* y, double c,
                      const double* z, double* out)
 {

@@ -464,11 +464,12 @@ __global__ __launch_bounds__(256) void k_spmv_v16(int64_t n_rows, const int64_t*
   double v[kSpmvRpg];
 #pragma unroll
   for (int i = 0; i < kSpmvRpg; ++i) {
+    // a lane past its row's end loads nothing (column 0, value 0, as k_spmv_blk):
+    // rb[i] is one past the arrays for an empty last row or an empty matrix
     const int64_t k = rb[i] + l16;
     const bool in = k < re[i];
-    const int64_t kk = in ? k : rb[i];
-    c[i] = cols[kk];
-    v[i] = in ? vals[kk] : 0.0;
+    c[i] = in ? cols[k] : 0;
+    v[i] = in ? vals[k] : 0.0;
   }
 #pragma unroll
   for (int i = 0; i < kSpmvRpg; ++i) s[i] = v[i] * x[c[i]];
@@ -1103,7 +1104,8 @@ __global__ __launch_bounds__(kThreads) void k_cg_init(int64_t n, const double* _
                                                       double* __restrict__ z, double* __restrict__ p,
                                                       const double* __restrict__ dinv,
                                                       const uint8_t* __restrict__ cons, double* __restrict__ partial,
-                                                      double* __restrict__ partial_free)
+                                                      double* __restrict__ partial_free,
+                                                      double* __restrict__ stuck = nullptr)
 {
   double s = 0.0, sf = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -1114,6 +1116,9 @@ __global__ __launch_bounds__(kThreads) void k_cg_init(int64_t n, const double* _
     p[i] = zi;
     s += ri * zi;
     if (!cons[i]) sf += ri * zi;
+    // a free row without a diagonal (dinv = 0) keeps z_i = p_i = 0: its residual is never
+    // reduced and r.z does not see it (every lane stores the same value)
+    if (stuck && !cons[i] && dinv[i] == 0.0 && ri != 0.0) *stuck = 1.0;
   }
   double bs = block_sum(s);
   double bf = block_sum(sf);
@@ -1583,6 +1588,7 @@ struct SpmvPlan {
   bool wide = false;    // 16-B loads of the segment (aligned bases)
   bool unroll = false;  // k_spmv_stream4u
   int64_t max_seg = 0;
+  int64_t seg256 = 0;   // rpb = kThreads: the largest segment of a kThreads-row block (max_seg: of a bs-row block)
   int64_t nblocks = 0;
   // rpb = -2: k_spmv_blk over the node-row structure (NB_DOF = blk_k)
   int blk_k = 0;
@@ -1592,6 +1598,7 @@ struct SpmvPlan {
   // rpb = -3: k_spmv_pat (pattern rows form their columns), rows per block bs
   const uint8_t* pat_flag = nullptr;
   PatOff po{};
+  int64_t pat_rows = 0;  // rows flagged for the pattern
   int bs = kThreads;
 };
 
@@ -1633,6 +1640,7 @@ SpmvPlan plan_spmv(Ctx& ctx, const int64_t* rows, int64_t n_rows, const int32_t*
   else if (hm * 8ull <= 64ull * 1024ull) {
     pl.rpb = kThreads;
     pl.max_seg = (int64_t)hm;
+    pl.seg256 = (int64_t)hm;
     pl.wide = (mode == 0 || mode == 3) && cols && vals && ((uintptr_t)cols & 15) == 0 && ((uintptr_t)vals & 15) == 0;
     pl.unroll = mode == 0;
     // AFEM_SPMV_STREAM_BS=64 / 128: the unrolled stream kernel in smaller row blocks (its segment
@@ -1732,7 +1740,7 @@ SpmvPlan plan_spmv_ls(Ctx& ctx, const LinearSystem& ls)
   // the pattern SpMV: the default for scalar systems (AFEM_SPMV=nopat or any other
   // diagnostic mode: the CSR kernels as they are)
   if ((!e || std::string(e) == "pat") && ls.blk_k <= 1 && ls.n_rows > 64 && ls.csr_cols && ls.csr_vals &&
-      pl.rpb == kThreads && pl.wide && pl.max_seg + 3 <= 4 * kThreads * kSpmvU) {
+      pl.rpb == kThreads && pl.wide && pl.seg256 + 3 <= 4 * kThreads * kSpmvU) {
     // the most frequent column-offset pattern among 256 rows spread over the
     // range (a structured box's interior stencil); rows that share it (k_pat_flags)
     constexpr int kSamples = 256;
@@ -1778,6 +1786,13 @@ SpmvPlan plan_spmv_ls(Ctx& ctx, const LinearSystem& ls)
         pl.rpb = -3;
         pl.po = po;
         pl.pat_flag = ls.pat_flag.p;
+        pl.pat_rows = (int64_t)hc;
+        // the pattern kernel's own block size from here on (AFEM_SPMV_STREAM_BS is the stream
+        // kernel's knob: its 64 / 128-row plan left in place made k_spmv_pat<64> run segments
+        // longer than its 4 * bs * kSpmvU products whenever the AFEM_SPMV_BS test below declined)
+        pl.bs = kThreads;
+        pl.max_seg = pl.seg256;
+        pl.nblocks = (ls.n_rows + kThreads - 1) / kThreads;
         // row blocks of 64 (the default: one wave per block, 7.7 KB of LDS, its barriers
         // wave-local): C2 0.503 vs 0.536 ms per CG iteration with 256, C4 5.64 vs 6.02
         // (r05am, one process); AFEM_SPMV_BS=128 / 256 the larger blocks
@@ -2078,6 +2093,23 @@ void ls_spmv(LinearSystem& ls, const double* x, double* y)
   launch_spmv(ctx, pl, ls.n_rows, ls.csr_rows, ls.csr_cols, ls.csr_vals, x, y, nullptr, ls.csr_nnz);
 }
 
+// diagnostic: the plan ls_spmv / ls_solve choose now (the planner itself runs)
+void ls_spmv_plan_info(LinearSystem& ls, afem_spmv_plan_info* out)
+{
+  Ctx& ctx = *ls.ctx;
+  require_csr(ls);
+  const SpmvPlan pl = plan_spmv_ls(ctx, ls);
+  out->rpb = pl.rpb;
+  out->wide = pl.wide ? 1 : 0;
+  out->unroll = pl.unroll ? 1 : 0;
+  out->bs = pl.bs;
+  out->blk_k = pl.rpb == -2 ? pl.blk_k : 0;
+  out->pat_len = pl.rpb == -3 ? pl.po.len : 0;
+  out->max_seg = pl.max_seg;
+  out->nblocks = pl.nblocks;
+  out->pat_rows = pl.rpb == -3 ? pl.pat_rows : 0;
+}
+
 namespace {
 void ls_solve_direct(LinearSystem& ls, afem_solve_stats* st)
 {
@@ -2293,7 +2325,7 @@ void ls_solve(LinearSystem& ls, afem_solve_stats* st)
                          ls.z.p, ls.p.p, ls.binv.p, ls.cons.p, ls.partial.p, ls.partial.p + vb);
     else
       hipLaunchKernelGGL(k_cg_init, dim3(vb), dim3(kThreads), 0, ctx.stream, n, ls.rhs.p, ls.q.p, ls.r.p, ls.z.p,
-                         ls.p.p, ls.dinv.p, ls.cons.p, ls.partial.p, ls.partial.p + vb);
+                         ls.p.p, ls.dinv.p, ls.cons.p, ls.partial.p, ls.partial.p + vb, ls.scal.p + 6);
     AFEM_LAUNCHED();
   };
   const bool warm = ls.opts.initial_guess == 1;
@@ -2306,8 +2338,11 @@ void ls_solve(LinearSystem& ls, afem_solve_stats* st)
   AFEM_LAUNCHED();
   if (ls.halo) halo_exchange(*ls.halo, ctx, ls.p.p);
   launch_spmv(ctx, pl, n, ls.csr_rows, ls.csr_cols, ls.csr_vals, ls.p.p, ls.q.p, nullptr, ls.csr_nnz);
+  // [0],[1]: r.z ping-pong, [2]: p.q, [3]: r0.z0 over free rows, [4]: r.r, [5]: z.q (flexible CG),
+  // [6]: not 0 when a free row without a diagonal starts with a residual (point Jacobi, k_cg_init)
+  double* scal = ls.scal.p;
+  AFEM_HIP(hipMemsetAsync(scal + 6, 0, sizeof(double), ctx.stream));
   cg_init();
-  double* scal = ls.scal.p;  // [0],[1]: r.z ping-pong, [2]: p.q, [3]: r0.z0 over free rows, [4]: r.r
   reduce_to(ctx, ls.partial.p, blk3 ? vb3 : vb, scal + 0);
   reduce_to(ctx, ls.partial.p + vb, blk3 ? vb3 : vb, scal + 3);
   Comm* comm = ls.halo ? ls.halo->comm : nullptr;
@@ -2595,8 +2630,9 @@ void ls_solve(LinearSystem& ls, afem_solve_stats* st)
   AFEM_LAUNCHED();
   reduce_to(ctx, ls.partial.p, vb, scal + 4);
   if (comm) comm_allreduce(comm, ctx, scal + 4, 1);
-  AFEM_HIP(hipMemcpyAsync(ls.pinned, scal, 5 * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
+  AFEM_HIP(hipMemcpyAsync(ls.pinned, scal, 7 * sizeof(double), hipMemcpyDeviceToHost, ctx.stream));
   ctx.sync();
+  const bool stuck = ls.pinned[6] != 0.0;  // a row the iteration cannot reach: never a success
   float ms = 0.f;
   AFEM_HIP(hipEventElapsedTime(&ms, ctx.ev0, ctx.ev1));
   rel = rz0 > 0 ? std::sqrt(std::fabs(ls.pinned[it & 1] / rz0)) : 0.0;
@@ -2618,7 +2654,7 @@ void ls_solve(LinearSystem& ls, afem_solve_stats* st)
       st->amg_complexity = 0.0;
     }
     st->iterations = it;
-    st->converged = fixed ? (rel <= o.rtol) : converged;
+    st->converged = !stuck && (fixed ? (rel <= o.rtol) : converged);
     st->rel_residual = rel;
     st->residual_norm = std::sqrt(std::fabs(ls.pinned[4]));
     st->solve_ms = ms;

@@ -592,7 +592,12 @@ int afem_ls_clear_values(afem_ls* ls);
  * femutils/DoFLinearSystem.cc:106-164) a direct dense LU below 500 rows or the
  * Jacobi-PCG whose initial guess lifts the constraint rows.
  * With a communicator attached the SpMV exchanges ghost values and the dot
- * products are summed over ranks (RCCL). */
+ * products are summed over ranks (RCCL).
+ * Degenerate systems: a free (non-constraint) row whose diagonal sums to 0 has
+ * no Jacobi inverse; the PCG leaves x_i = 0 there and, when that row's
+ * initial residual is not 0, reports converged = 0 whatever r.z says.  So a
+ * matrix without entries (nb_nz = 0) gives x = 0, converged only for b = 0;
+ * the direct solver answers such a matrix with AFEM_ERR_ARG (singular). */
 int afem_ls_solve(afem_ls* ls, afem_solve_stats* stats);
 /* ---- diagnostic: the multigrid / AMG preconditioner part by part.  Not part of
  * the reference's interface and not on any hot path; the tests hold every part
@@ -652,8 +657,29 @@ int afem_ls_precond_level_copy(afem_ls* ls, int32_t level, int64_t* row_ptr, int
                                double* dinv, uint8_t* cons, uint8_t* in, int32_t* agg, int64_t* agg_ptr,
                                int32_t* members);
 /* y[0:n_rows] = A x (x of length n_cols_local, ghost part exchanged first when
- * a communicator is attached).  Device pointers. */
+ * a communicator is attached).  Device pointers.  A row without entries gives
+ * exactly 0, a matrix without entries (nb_nz = 0) gives y = 0; no kernel reads
+ * columns / values outside [0, nb_nz). */
 int afem_ls_spmv(afem_ls* ls, const double* x, double* y);
+/* Diagnostic: the SpMV plan that afem_ls_spmv / afem_ls_solve choose for the
+ * current matrix under the variants currently set (the planner itself runs:
+ * the same function both call).  rpb: 256 the CSR-stream kernels (wide = 1:
+ * 16-B loads, k_spmv_stream4; with unroll = 1: k_spmv_stream4u; wide = 0:
+ * k_spmv_stream), 0 one lane per row (k_spmv_row), -1 16 lanes per row
+ * (k_spmv_v16), -2 node blocks (k_spmv_blk, blk_k = NB_DOF), -3 the pattern
+ * kernel (k_spmv_pat; pat_len offsets, pat_rows rows that match them). */
+typedef struct afem_spmv_plan_info {
+  int32_t rpb;       /* see above */
+  int32_t wide;      /* 16-B loads of the segment (16-B aligned columns / values) */
+  int32_t unroll;    /* the unrolled stream kernel */
+  int32_t bs;        /* rows per workgroup of the stream / pattern kernels */
+  int32_t blk_k;     /* rpb = -2: NB_DOF of the node blocks, else 0 */
+  int32_t pat_len;   /* rpb = -3: column offsets of the pattern, else 0 */
+  int64_t max_seg;   /* largest non-zero count of a bs-row block (stream / pattern kernels) */
+  int64_t nblocks;   /* workgroups of the launch */
+  int64_t pat_rows;  /* rpb = -3: rows flagged as pattern rows, else 0 */
+} afem_spmv_plan_info;
+int afem_ls_spmv_plan_info(afem_ls* ls, afem_spmv_plan_info* out);
 int afem_ls_destroy(afem_ls* ls);
 
 /* ---- time stepping (callers of the path: modules/elastodynamics, modules/passmo) */

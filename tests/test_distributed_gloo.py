@@ -73,39 +73,13 @@ def _worker(rank, world, port, out_q):
     rp, cols = O.sparsity(n_loc, n_own, m["cells"])
     vals, rhs = O.assemble_poisson(n_own, m["cells"], m["coords"], rp, cols, 5.5)
     O.dirichlet_penalty(m["dirichlet"], 0.5, 1e30, rp, cols, vals, rhs)
-    # distributed Jacobi-PCG: the sequence of ls_solve (linear_system.hip)
-    d = np.array([vals[rp[i]:rp[i + 1]][cols[rp[i]:rp[i + 1]] == i][0] for i in range(n_own)])
-    off = np.array([np.abs(vals[rp[i]:rp[i + 1]][cols[rp[i]:rp[i + 1]] != i]).sum() for i in range(n_own)])
-    dinv = np.where(d != 0, 1.0 / d, 0.0)                      # k_inv_diag
-    cons = np.abs(d) > 1e10 * off
-    p = np.zeros(n_loc)
-    x = np.where(cons, rhs * dinv, 0.0)                        # k_cg_x0
-    p[:n_own] = x
-    _halo(p, plan, rank)
-    r = rhs - O.spmv(rp, cols, vals, p)                        # k_cg_init
-    z = r * dinv
-    p[:n_own] = z
-    rz = _allsum(r @ z)
-    rz0 = _allsum((r * z)[~cons].sum())
-    if rz0 <= 0.0:
-        rz0 = rz
-    it, check, rtol = 0, 8, 1e-14
-    converged = rz == 0.0 or np.sqrt(abs(rz / rz0)) <= rtol
-    while not converged and it < 20000:
-        _halo(p, plan, rank)
-        q = O.spmv(rp, cols, vals, p)
-        pq = _allsum(p[:n_own] @ q)
-        alpha = rz / pq if pq != 0.0 else 0.0                  # k_cg_update
-        x += alpha * p[:n_own]
-        r -= alpha * q
-        z = r * dinv
-        rzn = _allsum(r @ z)
-        beta = rzn / rz if rz != 0.0 else 0.0                  # k_cg_dir
-        p[:n_own] = z + beta * p[:n_own]
-        rz = rzn
-        it += 1
-        if it % check == 0:
-            converged = np.sqrt(abs(rz / rz0)) <= rtol
+    # distributed Jacobi-PCG: the sequence of ls_solve (linear_system.hip), restated once in
+    # tests/pcg_ref.py; the halo exchange and the sums over ranks go through gloo
+    import pcg_ref
+
+    res = pcg_ref.pcg(rp, cols, vals, rhs, n_cols=n_loc, rtol=1e-14, max_iter=20000, check_every=8,
+                      allsum=_allsum, halo=lambda v: _halo(v, plan, rank))
+    x, it, converged = res["x"], res["iterations"], res["converged"]
     # owned rows vs the global matrix rows (global ids)
     l2g = m["local_to_global"]
     g = O.structured_mesh(3, N, nz=NZ)
