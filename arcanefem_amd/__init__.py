@@ -8,6 +8,6 @@ from ._capi import AfemError, LIB_PATH, load  # noqa: F401
 from .core import (BSRFormat, Communicator, Context, DoFLinearSystem, HipDoFLinearSystemFactory,  # noqa: F401
                    Mesh, applyNeumannToRhs, device_count, partition_rcb, set_variant, structured_halo_plan,
                    subdomain_plan)
-from .elastodynamics import Elastodynamics2D, Elastodynamics3D  # noqa: F401
+from .elastodynamics import Elastodynamics2D, Elastodynamics3D, Soildynamics2D  # noqa: F401
 
 __version__ = "0.1.0"

@@ -192,6 +192,7 @@ SIGNATURES = {
     "afem_bsr_assemble_elasticity_p1": [P, D, D],
     "afem_bsr_assemble_elasticity_p1_ex": [P, D, D, D, P, P, INT],
     "afem_bsr_assemble_elastodynamics_p1": [P, P, P, P, P, P, P, P, INT],
+    "afem_bsr_add_paraxial_p1": [P, P, I64, INT, D, D, P, P, P, P, P, P],
     "afem_apply_neumann": [P, INT, INT, P, I64, P, P, INT, P],
     "afem_vec_lincomb": [P, I64, D, P, D, P, D, P, P],
     "afem_newmark_update": [P, I64, D, D, D, P, P, P, P],
@@ -250,6 +251,9 @@ SIGNATURES = {
     "afem_elastodynamics_set_dirichlet_vectorial": [P, P, I64, P, ctypes.c_uint, INT, INT],
     "afem_elastodynamics_set_traction": [P, P, I64, P, ctypes.c_uint, INT],
     "afem_elastodynamics_set_traction_table": [P, INT, P, P, I64],
+    "afem_elastodynamics_set_wave_speeds": [P, D, D],
+    "afem_elastodynamics_set_paraxial": [P, P, I64, INT],
+    "afem_elastodynamics_set_double_couple": [P, P, I64, P, I64, P, I64, P, I64, P, P, I64, INT],
     "afem_elastodynamics_set_time_step": [P, D],
     "afem_elastodynamics_state": [P, PP, PP, PP],
     "afem_elastodynamics_operators": [P, ctypes.POINTER(CsrView), PP, PP, PP, P],

@@ -294,6 +294,21 @@ class BSRFormat:
              ctypes.c_void_p(a_dptr), ctypes.c_void_p(fixed_dptr) if fixed_dptr else None, ctypes.c_void_p(rhs_dptr),
              _rhs_mode(rhs_mode))
 
+    def addParaxialP1(self, faces, cp: float, cs: float, p, u_dptr: int, v_dptr: int, a_dptr: int,
+                      fixed_dptr: int | None, rhs_dptr: int):
+        """Block-2 triangles: the paraxial boundary terms of
+        modules/soildynamics on the boundary edges faces[n, 2] (local node
+        ids), added to the values (the EDGE2 matrix) and to rhs (the edge loop
+        over U, V, A; device, 2 per local node); p = the module's (c7, c8,
+        c9), fixed_dptr = one byte per owned DoF (or None)."""
+        if len(p) != 3:
+            raise ValueError("p needs the 3 paraxial constants")
+        faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 2)
+        pp = (ctypes.c_double * 3)(*[float(x) for x in p])
+        call("afem_bsr_add_paraxial_p1", self.h, _ptr(faces) if faces.size else None, faces.shape[0], C.AFEM_MEM_HOST,
+             float(cp), float(cs), pp, ctypes.c_void_p(u_dptr), ctypes.c_void_p(v_dptr), ctypes.c_void_p(a_dptr),
+             ctypes.c_void_p(fixed_dptr) if fixed_dptr else None, ctypes.c_void_p(rhs_dptr))
+
     def resetMatrixValues(self):
         call("afem_bsr_reset_values", self.h)
 

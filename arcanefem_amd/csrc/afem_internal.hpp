@@ -357,6 +357,22 @@ struct HandOver {
   DevBuf<double> vals;
 };
 
+// Paraxial (absorbing) boundary edges of a block-2 triangle matrix
+// (modules/soildynamics/FemModule.cc: EDGE2 element matrix :1376-1486, RHS
+// edge loop :870-936), regrouped per owned boundary node for k_paraxial2
+// (dynamics.hip): node i = nodes[i] owns the edge entries eptr[i] ..
+// eptr[i + 1] (registration order), each with the edge's other end, its
+// geometry geo[4 e] = L, nx^2, ny^2, nx ny and the value position of the
+// (node, other) block; dbase / stride place the node's diagonal block.  Entry
+// (r, c) of a block sits at base + r * stride + c in either value layout.
+struct ParaxialPlan {
+  int64_t n = 0;  // owned boundary nodes = lanes
+  DevBuf<int32_t> nodes, eptr, other, stride;
+  DevBuf<double> geo;
+  DevBuf<int64_t> dbase, obase;
+  std::vector<int32_t> key;  // the face list it was built from (afem_bsr_add_paraxial_p1's cache)
+};
+
 struct Bsr {
   Mesh* mesh = nullptr;
   int nb_dof = 1;
@@ -373,6 +389,7 @@ struct Bsr {
   FunctorPlan fplan;         // cell-unit plan of the generic assembly (built at its first use)
   HandOver hand;             // toLinearSystem in the caller's numbering (afem_bsr_to_csr32_mapped)
   DevBuf<double> cube_stage; // staged canonical cube path: one 128-B line per lattice row (cubes.hip)
+  std::unique_ptr<ParaxialPlan> pplan;  // afem_bsr_add_paraxial_p1: the plan of the last face list
 };
 void bsr_csr32_mapped_build(Bsr& b, const int32_t* dof_of_host, int64_t n_dof_rows);
 double* bsr_csr32_mapped_values(Bsr& b);  // the values in the mapped CSR order (gathered, or aliased)
@@ -670,10 +687,25 @@ struct Elastodynamics {
     std::vector<double> times, values;  // CaseTable (values: 2 per time); empty: constant
   };
   std::vector<Traction2> trac2;
+  // modules/soildynamics on the 2D loop: the wave speeds (:261-280; 0 until a paraxial block needs
+  // them), the paraxial edges of all blocks in registration order and their plan (one launch per
+  // step), and the double-couple sources (:946-987): DoFs and signs uploaded once, the step
+  // scales them by the table's force
+  double cp = 0.0, cs = 0.0;
+  std::vector<int32_t> par_faces;
+  ParaxialPlan par;
+  struct DoubleCouple2 {
+    DevBuf<int32_t> dofs;
+    DevBuf<double> sign;
+    std::vector<int32_t> hdofs;
+    std::vector<double> times, values;
+  };
+  std::vector<DoubleCouple2> dc2;
   afem_solve_stats last{};
   // afem_elastodynamics_profile: per-phase events of every step
   bool profile = false;
   hipEvent_t ev[6] = {};
+  hipEvent_t ev_dc[2] = {};  // around the double-couple assignment (counted in rhs_ms)
   afem_step_timing timing{};
 };
 Elastodynamics* dyn_create(Mesh* mesh, Comm* comm, const afem_newmark_params* prm, const int32_t* fixed_nodes,
@@ -689,6 +721,18 @@ void dyn_set_dirichlet_vectorial(Elastodynamics* d, const int32_t* nodes, int64_
 void dyn_set_traction(Elastodynamics* d, const int32_t* face_nodes, int64_t n_faces, const double t[2], unsigned mask,
                       int mem);
 void dyn_set_traction_table(Elastodynamics* d, int index, const double* times, const double* values, int64_t n);
+// modules/soildynamics on the 2D loop (AFEM_ERR_NOT_IMPL on a 3D handle, with damping or generalized-alpha)
+void dyn_set_wave_speeds(Elastodynamics* d, double cp, double cs);
+void dyn_set_paraxial(Elastodynamics* d, const int32_t* face_nodes, int64_t n_faces, int mem);
+void dyn_set_double_couple(Elastodynamics* d, const int32_t* const nodes[4], const int64_t n_nodes[4], const double* times,
+                           const double* values, int64_t n, int mem);
+// the plan of a face list (host, 2 per edge) on b's structure and value layout; edges without an owned end are dropped
+void paraxial_plan_build(Bsr& b, const std::vector<int32_t>& faces, ParaxialPlan& plan);
+// values += the paraxial LHS, rhs += the paraxial RHS from u, v, a (2 per local node), one launch
+void paraxial_add(Ctx& ctx, const ParaxialPlan& plan, double cp, double cs, const double p[3], const double* u,
+                  const double* v, const double* a, const uint8_t* fixed, double* values, double* rhs);
+// x[ids[i]] = scale * vals[i] (device arrays)
+void vec_scatter_scaled(Ctx& ctx, int64_t n, const int32_t* ids, const double* vals, double scale, double* x);
 // CaseTable::CurveLinear: piecewise linear in (times, values[n][2]), constant outside
 void table_interp2(const std::vector<double>& times, const std::vector<double>& values, double t, double out[2]);
 void dyn_destroy(Elastodynamics* d);

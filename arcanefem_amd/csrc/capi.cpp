@@ -484,6 +484,7 @@ int afem_bsr_compute_sparsity(afem_bsr* b)
   b->has_sparsity = false;
   b->fplan = FunctorPlan();
   b->hand = HandOver();
+  b->pplan.reset();
   build_structure(*b->mesh, b->s, b->nb_dof);
   b->values.alloc((size_t)b->s.nnz * b->nb_dof * b->nb_dof);
   AFEM_HIP(hipMemsetAsync(b->values.p, 0, b->values.bytes(), b->mesh->ctx->stream));
@@ -565,6 +566,40 @@ int afem_bsr_assemble_elastodynamics_p1(afem_bsr* b, const double c[11], const d
   AFEM_REQUIRE(rhs_mode == AFEM_RHS_ADD || rhs_mode == AFEM_RHS_SET, AFEM_ERR_ARG, "unknown rhs_mode");
   b->mesh->ctx->set_device();
   assemble_elastodynamics_tri(*b, c, body_force, u, v, a, fixed, rhs, rhs_mode == AFEM_RHS_ADD ? 1 : 0);
+  API_END
+}
+
+int afem_bsr_add_paraxial_p1(afem_bsr* b, const int32_t* face_nodes, int64_t n_faces, int mem, double cp, double cs,
+                             const double p[3], const double* u, const double* v, const double* a, const uint8_t* fixed,
+                             double* rhs)
+{
+  API_BEGIN
+  AFEM_RANGE("afem: paraxial boundary (EDGE2 on TRIA3)");
+  NOT_NULL(b);
+  AFEM_REQUIRE(b->has_sparsity, AFEM_ERR_STATE, "assembleBilinear called before computeSparsity");
+  AFEM_REQUIRE(b->mesh->nv == 3 && b->nb_dof == 2, AFEM_ERR_NOT_IMPL,
+               "the paraxial boundary terms are implemented for NB_DOF = 2 on triangles");
+  AFEM_REQUIRE(n_faces >= 0 && (n_faces == 0 || face_nodes), AFEM_ERR_ARG, "afem_bsr_add_paraxial_p1: bad face list");
+  NOT_NULL(p);
+  NOT_NULL(u);
+  NOT_NULL(v);
+  NOT_NULL(a);
+  NOT_NULL(rhs);
+  Ctx& ctx = *b->mesh->ctx;
+  ctx.set_device();
+  // the plan of the last face list is kept: a caller that repeats its list pays for the comparison only
+  std::vector<int32_t> faces(2 * n_faces);
+  if (n_faces) {
+    AFEM_HIP(hipMemcpyAsync(faces.data(), face_nodes, faces.size() * sizeof(int32_t),
+                            mem == AFEM_MEM_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost, ctx.stream));
+    ctx.sync();
+  }
+  if (!b->pplan || b->pplan->key != faces) {
+    std::unique_ptr<ParaxialPlan> plan(new ParaxialPlan());
+    paraxial_plan_build(*b, faces, *plan);
+    b->pplan = std::move(plan);
+  }
+  paraxial_add(ctx, *b->pplan, cp, cs, p, u, v, a, fixed, b->values.p, rhs);
   API_END
 }
 
@@ -1556,6 +1591,35 @@ int afem_elastodynamics_set_traction_table(afem_elastodynamics* h, int traction_
   API_BEGIN
   NOT_NULL(h);
   dyn_set_traction_table(h->d, traction_index, times, values, n);
+  API_END
+}
+
+int afem_elastodynamics_set_wave_speeds(afem_elastodynamics* h, double cp, double cs)
+{
+  API_BEGIN
+  NOT_NULL(h);
+  dyn_set_wave_speeds(h->d, cp, cs);
+  API_END
+}
+
+int afem_elastodynamics_set_paraxial(afem_elastodynamics* h, const int32_t* face_nodes, int64_t n_faces, int mem)
+{
+  API_BEGIN
+  NOT_NULL(h);
+  dyn_set_paraxial(h->d, face_nodes, n_faces, mem);
+  API_END
+}
+
+int afem_elastodynamics_set_double_couple(afem_elastodynamics* h, const int32_t* north, int64_t n_north,
+                                          const int32_t* south, int64_t n_south, const int32_t* east, int64_t n_east,
+                                          const int32_t* west, int64_t n_west, const double* times, const double* values,
+                                          int64_t n, int mem)
+{
+  API_BEGIN
+  NOT_NULL(h);
+  const int32_t* const nodes[4] = { north, south, east, west };
+  const int64_t counts[4] = { n_north, n_south, n_east, n_west };
+  dyn_set_double_couple(h->d, nodes, counts, times, values, n, mem);
   API_END
 }
 

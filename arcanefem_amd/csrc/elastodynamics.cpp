@@ -25,6 +25,14 @@
 // blocks (Penalty, RowElimination, RowColumnElimination; NULL components), the
 // re-imposition of the constrained values after the solve (:1416-1417) and
 // the Newmark update follow.  One subdomain.
+//
+// modules/soildynamics/FemModule.cc runs on that 2D step too: paraxial
+// (absorbing) boundaries -- the EDGE2 matrix on the LHS (:1376-1486) and the
+// edge loop over U, V, A on the RHS (:870-936), all blocks of a handle in one
+// launch from a plan built at registration (paraxial_plan_build, k_paraxial2)
+// -- right after the fused kernel, and the force-based double couple
+// (:946-987), an assignment of +-F to four node groups' RHS entries right
+// before the solve.  Newmark-beta without damping only (:321).
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -35,6 +43,33 @@
 namespace afem {
 
 namespace {
+
+// A profiled step makes the PCG time its preconditioner applications
+// (opts.profile_comm = 1) and puts the caller's value back after the solve --
+// also when the solve throws, so that an error leaves the options as they were.
+struct ProfileCommGuard {
+  afem_solver_opts& o;
+  int32_t saved;
+  ProfileCommGuard(afem_solver_opts& opts, bool on) : o(opts), saved(opts.profile_comm)
+  {
+    if (on) o.profile_comm = 1;
+  }
+  void restore() { o.profile_comm = saved; }
+  ~ProfileCommGuard() { restore(); }
+  ProfileCommGuard(const ProfileCommGuard&) = delete;
+  ProfileCommGuard& operator=(const ProfileCommGuard&) = delete;
+};
+
+// CaseTable::CurveLinear with one value per time: piecewise linear, constant outside
+double table_interp1(const std::vector<double>& times, const std::vector<double>& values, double t)
+{
+  const size_t n = times.size();
+  if (t <= times.front() || n == 1) return values[0];
+  if (t >= times.back()) return values[n - 1];
+  const size_t k = std::upper_bound(times.begin(), times.end(), t) - times.begin();  // times[k-1] <= t < times[k]
+  const double w = (t - times[k - 1]) / (times[k] - times[k - 1]);
+  return values[k - 1] + w * (values[k] - values[k - 1]);
+}
 
 void halo_for(LinearSystem& ls, Comm* comm, Mesh& m)
 {
@@ -209,13 +244,28 @@ void dyn_step_tri(Elastodynamics* d, afem_solve_stats* st)
   auto mark = [&](int i) {
     if (prof) AFEM_HIP(hipEventRecord(d->ev[i], ctx.stream));
   };
-  const int32_t prof_opt = d->ls.opts.profile_comm;
-  if (prof) d->ls.opts.profile_comm = 1;
+  // a double-couple DoF that a Dirichlet block constrains: the assignment would undo the condition's RHS
+  for (const auto& dc : d->dc2)
+    for (int32_t dof : dc.hdofs)
+      AFEM_REQUIRE(!d->dir_dofs.count(dof), AFEM_ERR_ARG,
+                   "elastodynamics step: a double-couple DoF is constrained by a Dirichlet condition");
+  ProfileCommGuard prof_guard(d->ls.opts, prof);
   mark(0);
   // LHS c0 M + K(c1, c2) and the whole RHS of :645-867 in one pass (set mode)
   const double f[2] = { d->p.body_force[0], d->p.body_force[1] };
   assemble_elastodynamics_tri(d->K, d->c, f, d->U.p, d->V.p, d->A.p, d->fixed2.p, d->ls.rhs.p, 0);
   mark(1);
+  // paraxial boundaries (modules/soildynamics/FemModule.cc): the EDGE2 matrix added to the LHS
+  // (:1376-1486) and the edge loop over U, V, A to the RHS (:870-936), all blocks in one launch
+  if (d->par.n) {
+    const double rho = d->p.rho, dt = d->p.dt, gamma = d->gamma, beta = d->beta;
+    // the module's c7 .. c9 (:297-299) -- not the fused kernel's damping terms c[7 .. 10], zero here
+    const double p[3] = { rho * gamma / beta / dt, rho * (1. - gamma / beta), rho * dt * (1. - gamma / (2. * beta)) };
+    const double mu = 0.5 * d->mu2;  // wave speeds of E, nu or lambda, mu (:261-273) unless given (:275-278)
+    const double cs = d->cs > 0 ? d->cs : std::sqrt(mu / rho);
+    const double cp = d->cp > 0 ? d->cp : std::sqrt((d->lambda + 2. * mu) / rho);
+    paraxial_add(ctx, d->par, cp, cs, p, d->U.p, d->V.p, d->A.p, d->fixed2.p, d->K.values.p, d->ls.rhs.p);
+  }
   // tractions t_i |e| / 2 per face node on the unfixed DoFs (:880-967), at the step's time for a table
   for (const auto& tr : d->trac2) {
     double t[2] = { tr.t[0], tr.t[1] };
@@ -230,9 +280,18 @@ void dyn_step_tri(Elastodynamics* d, afem_solve_stats* st)
   // warm start from the Newmark predictor, as in 3D
   vec_lincomb(ctx, d->n, 1.0, d->U.p, d->p.dt, d->V.p, d->p.dt * d->p.dt * (0.5 - d->beta), d->A.p, d->ls.sol.p);
   d->ls.opts.initial_guess = 1;
+  // double couple (modules/soildynamics/FemModule.cc:946-987): after everything else the listed DoFs'
+  // RHS entries are ASSIGNED +-F, F = the source's table at the step's time
+  const bool prof_dc = prof && !d->dc2.empty();  // timed apart: it belongs to rhs_ms, not to bc_ms
+  if (prof_dc) AFEM_HIP(hipEventRecord(d->ev_dc[0], ctx.stream));
+  for (const auto& dc : d->dc2) {
+    const double F = table_interp1(dc.times, dc.values, d->t);
+    vec_scatter_scaled(ctx, (int64_t)dc.dofs.n, dc.dofs.p, dc.sign.p, F, d->ls.rhs.p);
+  }
+  if (prof_dc) AFEM_HIP(hipEventRecord(d->ev_dc[1], ctx.stream));
   mark(3);
   ls_solve(d->ls, &d->last);
-  d->ls.opts.profile_comm = prof_opt;
+  prof_guard.restore();
   mark(4);
   // the constrained values re-imposed on the solution (_solve, :1416-1417)
   if (d->imp_ids.n) vec_scatter(ctx, (int64_t)d->imp_ids.n, d->imp_ids.p, d->imp_vals.p, d->ls.sol.p);
@@ -246,9 +305,11 @@ void dyn_step_tri(Elastodynamics* d, afem_solve_stats* st)
     float tot = 0.f;
     AFEM_HIP(hipEventElapsedTime(&tot, d->ev[0], d->ev[5]));
     afem_step_timing& t = d->timing;
+    float dc_ms = 0.f;
+    if (prof_dc) AFEM_HIP(hipEventElapsedTime(&dc_ms, d->ev_dc[0], d->ev_dc[1]));
     t.assemble_ms = ms[0];
-    t.rhs_ms = ms[1];
-    t.bc_ms = ms[2];
+    t.rhs_ms = ms[1] + dc_ms;  // the paraxial launch, the tractions and the double-couple assignment
+    t.bc_ms = ms[2] - dc_ms;
     t.solve_ms = ms[3];
     t.precond_ms = d->last.precond_ms;
     t.update_ms = ms[4];
@@ -303,6 +364,7 @@ void dyn_set_lame(Elastodynamics* d, double lambda, double mu)
   AFEM_REQUIRE(mu > 0 && lambda + mu > 0, AFEM_ERR_ARG, "afem_elastodynamics_set_lame: bad Lame parameters");
   d->lambda = lambda;
   d->mu2 = 2 * mu;
+  d->cp = d->cs = 0.0;  // the paraxial wave speeds follow the Lame parameters again (FemModule.cc:268-273)
   dyn_coefficients(d);
 }
 
@@ -396,6 +458,147 @@ void dyn_set_traction_table(Elastodynamics* d, int index, const double* times, c
   auto& tr = d->trac2[index];
   tr.times.assign(times, times + n);
   tr.values.assign(values, values + 2 * n);
+}
+
+// ---------------------------------------------------------------- modules/soildynamics on the 2D loop
+void paraxial_plan_build(Bsr& b, const std::vector<int32_t>& faces, ParaxialPlan& plan)
+{
+  Ctx& ctx = *b.mesh->ctx;
+  const Mesh& m = *b.mesh;
+  const int64_t n_faces = (int64_t)faces.size() / 2, n_own = b.s.n_rows;
+  const std::vector<double> xyz = to_host(ctx, m.coords.p, 3 * m.n_nodes, AFEM_MEM_DEVICE);
+  const std::vector<int64_t> rp = to_host(ctx, b.s.row_ptr.p, n_own + 1, AFEM_MEM_DEVICE);
+  const std::vector<int32_t> cols = to_host(ctx, b.s.cols.p, b.s.nnz, AFEM_MEM_DEVICE);
+  struct Entry {
+    int32_t other;
+    double g[4];
+  };
+  std::map<int32_t, std::vector<Entry>> by_node;  // owned node -> its edges in registration order
+  for (int64_t f = 0; f < n_faces; ++f) {
+    const int32_t ends[2] = { faces[2 * f], faces[2 * f + 1] };
+    AFEM_REQUIRE(ends[0] >= 0 && ends[0] < m.n_nodes && ends[1] >= 0 && ends[1] < m.n_nodes, AFEM_ERR_ARG,
+                 "paraxial face node id out of range");
+    AFEM_REQUIRE(ends[0] != ends[1], AFEM_ERR_ARG, "paraxial face with twice the same node");
+    // length and unit normal (_computeEdgeLength2 / _computeEdgeNormal2); only nx^2, ny^2 and nx ny enter
+    const double dx = xyz[3 * ends[1]] - xyz[3 * ends[0]], dy = xyz[3 * ends[1] + 1] - xyz[3 * ends[0] + 1];
+    const double len = std::sqrt(dx * dx + dy * dy);
+    AFEM_REQUIRE(len > 0, AFEM_ERR_ARG, "paraxial face of zero length");
+    const double nx = dy / len, ny = -dx / len;
+    for (int k = 0; k < 2; ++k)  // an end that is a ghost has no row here (the module's isOwn() guards)
+      if (ends[k] < n_own) by_node[ends[k]].push_back({ ends[1 - k], { len, nx * nx, ny * ny, nx * ny } });
+  }
+  std::vector<int32_t> nodes, eptr{ 0 }, other, stride;
+  std::vector<double> geo;
+  std::vector<int64_t> dbase, obase;
+  auto block_at = [&](int32_t row, int32_t col, int64_t* base, int32_t* st) {
+    const auto rb = cols.begin() + rp[row], re = cols.begin() + rp[row + 1];
+    const auto it = std::lower_bound(rb, re, col);
+    AFEM_REQUIRE(it != re && *it == col, AFEM_ERR_ARG, "paraxial face is not an edge of the mesh");
+    const int64_t k = it - cols.begin(), len = rp[row + 1] - rp[row];
+    *base = b.order_per_block ? 4 * k : 4 * rp[row] + 2 * (k - rp[row]);
+    *st = b.order_per_block ? 2 : (int32_t)(2 * len);
+  };
+  for (const auto& kv : by_node) {
+    int64_t base;
+    int32_t st;
+    block_at(kv.first, kv.first, &base, &st);
+    nodes.push_back(kv.first);
+    dbase.push_back(base);
+    stride.push_back(st);
+    for (const Entry& e : kv.second) {
+      block_at(kv.first, e.other, &base, &st);
+      other.push_back(e.other);
+      obase.push_back(base);
+      geo.insert(geo.end(), e.g, e.g + 4);
+    }
+    AFEM_REQUIRE(other.size() < ((size_t)1 << 31), AFEM_ERR_LIMIT, "too many paraxial faces");
+    eptr.push_back((int32_t)other.size());
+  }
+  upload(ctx, plan.nodes, nodes);
+  upload(ctx, plan.eptr, eptr);
+  upload(ctx, plan.other, other);
+  upload(ctx, plan.stride, stride);
+  upload(ctx, plan.geo, geo);
+  upload(ctx, plan.dbase, dbase);
+  upload(ctx, plan.obase, obase);
+  plan.n = (int64_t)nodes.size();
+  plan.key = faces;
+}
+
+namespace {
+// the module's own FATAL (:321) and what the paraxial constants are derived for
+void require_soil(const Elastodynamics* d, const char* what)
+{
+  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, (std::string(what) + ": the 2D loop's entry").c_str());
+  AFEM_REQUIRE(d->p.scheme == 0 && d->p.etam == 0.0 && d->p.etak == 0.0, AFEM_ERR_NOT_IMPL,
+               (std::string(what) + ": Only Newmark-beta works for time-discretization (no damping, no generalized-alpha)")
+                   .c_str());
+}
+}  // namespace
+
+void dyn_set_wave_speeds(Elastodynamics* d, double cp, double cs)
+{
+  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, "afem_elastodynamics_set_wave_speeds: the 2D loop's entry");
+  AFEM_REQUIRE(d->p.rho > 0, AFEM_ERR_ARG, "afem_elastodynamics_set_wave_speeds: rho must be > 0");
+  const double mu = cs * cs * d->p.rho, lambda = cp * cp * d->p.rho - 2 * mu;  // FemModule.cc:275-278
+  AFEM_REQUIRE(cp > 0 && cs > 0 && lambda + mu > 0, AFEM_ERR_ARG, "afem_elastodynamics_set_wave_speeds: bad wave speeds");
+  d->lambda = lambda;
+  d->mu2 = 2 * mu;
+  d->cp = cp;
+  d->cs = cs;
+  dyn_coefficients(d);
+}
+
+void dyn_set_paraxial(Elastodynamics* d, const int32_t* face_nodes, int64_t n_faces, int mem)
+{
+  require_soil(d, "afem_elastodynamics_set_paraxial");
+  AFEM_REQUIRE(n_faces >= 0 && (n_faces == 0 || face_nodes), AFEM_ERR_ARG, "afem_elastodynamics_set_paraxial: bad face list");
+  AFEM_REQUIRE(d->p.rho > 0, AFEM_ERR_ARG, "afem_elastodynamics_set_paraxial: rho must be > 0");
+  if (n_faces == 0) return;
+  Ctx& ctx = *d->ctx;
+  ctx.set_device();
+  const std::vector<int32_t> fn = to_host(ctx, face_nodes, 2 * n_faces, mem);
+  std::vector<int32_t> all = d->par_faces;
+  all.insert(all.end(), fn.begin(), fn.end());
+  ParaxialPlan plan;
+  paraxial_plan_build(d->K, all, plan);  // throws before the handle changes
+  d->par = std::move(plan);
+  d->par_faces = std::move(all);
+}
+
+void dyn_set_double_couple(Elastodynamics* d, const int32_t* const nodes[4], const int64_t n_nodes[4], const double* times,
+                           const double* values, int64_t n, int mem)
+{
+  require_soil(d, "afem_elastodynamics_set_double_couple");
+  AFEM_REQUIRE(n >= 1 && times && values, AFEM_ERR_ARG, "afem_elastodynamics_set_double_couple: empty table");
+  for (int64_t i = 1; i < n; ++i)
+    AFEM_REQUIRE(times[i] > times[i - 1], AFEM_ERR_ARG, "afem_elastodynamics_set_double_couple: times must increase");
+  Ctx& ctx = *d->ctx;
+  ctx.set_device();
+  // north: rhs[2 v] = F, south: rhs[2 v] = -F, east: rhs[2 v + 1] = -F, west: rhs[2 v + 1] = F (:966-985); a DoF
+  // named twice keeps the last assignment, as the module's successive loops
+  static const int comp[4] = { 0, 0, 1, 1 };
+  static const double sgn[4] = { 1.0, -1.0, -1.0, 1.0 };
+  std::map<int32_t, double> m;
+  for (int g = 0; g < 4; ++g) {
+    AFEM_REQUIRE(n_nodes[g] >= 0 && (n_nodes[g] == 0 || nodes[g]), AFEM_ERR_ARG,
+                 "afem_elastodynamics_set_double_couple: bad node list");
+    for (int32_t v : to_host(ctx, nodes[g], n_nodes[g], mem)) {
+      AFEM_REQUIRE(v >= 0 && v < d->mesh->n_nodes, AFEM_ERR_ARG, "double-couple node id out of range");
+      if (v < d->mesh->n_own) m[2 * v + comp[g]] = sgn[g];
+    }
+  }
+  Elastodynamics::DoubleCouple2 dc;
+  std::vector<double> s;
+  for (const auto& kv : m) {
+    dc.hdofs.push_back(kv.first);
+    s.push_back(kv.second);
+  }
+  upload(ctx, dc.dofs, dc.hdofs);
+  upload(ctx, dc.sign, s);
+  dc.times.assign(times, times + n);
+  dc.values.assign(values, values + n);
+  d->dc2.push_back(std::move(dc));
 }
 
 Elastodynamics* dyn_create(Mesh* mesh, Comm* comm, const afem_newmark_params* prm, const int32_t* fixed_nodes,
@@ -541,8 +744,7 @@ void dyn_step(Elastodynamics* d, afem_solve_stats* st)
     auto mark = [&](int i) {
       if (prof) AFEM_HIP(hipEventRecord(d->ev[i], ctx.stream));
     };
-    const int32_t prof_opt = d->ls.opts.profile_comm;
-    if (prof) d->ls.opts.profile_comm = 1;  // the PCG times its preconditioner applications
+    ProfileCommGuard prof_guard(d->ls.opts, prof);  // the PCG times its preconditioner applications
     mark(0);
     // LHS c0 M + K(c1, c2) and the body force (rhs = f |K|/4), re-assembled on the fixed structure
     assemble_elasticity_tet(d->K, c[1], c[2], c[0], f, d->ls.rhs.p, 0);
@@ -572,7 +774,7 @@ void dyn_step(Elastodynamics* d, afem_solve_stats* st)
     d->ls.opts.initial_guess = 1;
     mark(3);
     ls_solve(d->ls, &d->last);
-    d->ls.opts.profile_comm = prof_opt;
+    prof_guard.restore();
     mark(4);
     // the imposed values re-applied to the solution (_doSolve, :2369-2371)
     if (d->imp_ids.n) vec_scatter(ctx, (int64_t)d->imp_ids.n, d->imp_ids.p, d->imp_vals.p, d->ls.sol.p);
@@ -651,8 +853,10 @@ void dyn_set_time_step(Elastodynamics* d, double dt)
 void dyn_profile(Elastodynamics* d, bool on)
 {
   d->ctx->set_device();
-  if (on && !d->ev[0])
+  if (on && !d->ev[0]) {
     for (auto& e : d->ev) AFEM_HIP(hipEventCreate(&e));
+    for (auto& e : d->ev_dc) AFEM_HIP(hipEventCreate(&e));
+  }
   d->profile = on;
   afem_step_timing& t = d->timing;
   t.nnz_blocks = d->K.s.nnz;
@@ -667,6 +871,8 @@ void dyn_destroy(Elastodynamics* d)
   d->ctx->set_device();
   (void)hipStreamSynchronize(d->ctx->stream);
   for (auto& e : d->ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : d->ev_dc)
     if (e) (void)hipEventDestroy(e);
   if (d->ls.pinned) (void)hipHostFree(d->ls.pinned);
   for (LinearSystem* l : { &d->lsm, &d->lsl, &d->lsu })

@@ -1,5 +1,7 @@
 """Elastodynamics time stepping on the assembly + CG path: 3D (BASELINE config C5)
-and the reference module's own 2D case (Elastodynamics2D, at the end).
+and the reference module's own 2D case (Elastodynamics2D, at the end), with the
+soil-dynamics module on top of it (Soildynamics2D: paraxial boundaries and a
+double-couple source, modules/soildynamics/FemModule.cc).
 
 Thin host mirror of the native time loop behind the C ABI
 (``afem_elastodynamics_*``, arcanefem_amd/csrc/elastodynamics.cpp), which
@@ -263,3 +265,65 @@ class Elastodynamics2D(Elastodynamics3D):
         d = super().operators()
         d.pop("mass")
         return d
+
+
+class Soildynamics2D(Elastodynamics2D):
+    """The module modules/soildynamics: the block-2 TRIA3 step of
+    Elastodynamics2D plus paraxial (absorbing) boundaries -- an EDGE2 matrix on
+    the LHS (FemModule.cc:1376-1486) and an edge loop over U, V, A on the RHS
+    (:870-936), one HIP launch per step for all blocks -- and a force-based
+    double-couple source (:946-987).  Material: cp and cs (mu = cs^2 rho,
+    lambda = cp^2 rho - 2 mu, :275-278), lam and mu, or E and nu (:261-273).
+    Newmark-beta without damping only, as the module (:321).  setTraction and
+    setDirichlet are Elastodynamics2D's.
+    """
+
+    def __init__(self, ctx: Context, mesh: Mesh, rho: float, dt: float, cp: float | None = None,
+                 cs: float | None = None, lam: float | None = None, mu: float | None = None, E: float | None = None,
+                 nu: float | None = None, body_force=(None, None), time_discretization: str = "newmark-beta",
+                 alpm: float = 0.0, alpf: float = 0.0, **kw):
+        if mesh.dim != 2:
+            raise ValueError("Soildynamics2D needs a triangle mesh")
+        if time_discretization.lower() not in SCHEMES:
+            raise ValueError("Only Newmark-beta | Generalized-alpha are supported for time-discretization")
+        if SCHEMES[time_discretization.lower()] != 0:
+            raise ValueError("Only Newmark-beta works for time-discretization Generalized-alpha WIP")
+        pairs = [(cp, cs), (lam, mu), (E, nu)]
+        if any((a is None) != (b is None) for a, b in pairs) or sum(a is not None for a, _ in pairs) != 1:
+            raise ValueError("give the material as cp and cs, as lam and mu, or as E and nu")
+        if cp is not None:
+            mu = float(cs) * float(cs) * rho
+            lam = float(cp) * float(cp) * rho - 2.0 * mu
+        # alpm / alpf of a deck are ignored by Newmark-beta (FemModule.cc:283-300)
+        super().__init__(ctx, mesh, rho, dt, lam=lam, mu=mu, E=E, nu=nu, body_force=body_force,
+                         time_discretization=time_discretization, **kw)
+        if cp is not None:
+            try:
+                call("afem_elastodynamics_set_wave_speeds", self.h, float(cp), float(cs))
+            except Exception:
+                self.close()
+                raise
+
+    def setParaxial(self, faces):
+        """One paraxial-boundary-condition block: the group's boundary edges
+        (faces[n, 2], local node ids).  Blocks accumulate."""
+        faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 2)
+        call("afem_elastodynamics_set_paraxial", self.h, ctypes.c_void_p(faces.ctypes.data) if faces.size else None,
+             faces.shape[0], C.AFEM_MEM_HOST)
+
+    def setDoubleCouple(self, north, south, east, west, table):
+        """One double-couple block (force-based): the four node groups (any may
+        be empty) and table = (times[n], values[n]), the force F of the
+        double-couple-input-file; each step assigns rhs[2 north] = F,
+        rhs[2 south] = -F, rhs[2 east + 1] = -F, rhs[2 west + 1] = F at the
+        step's time.  Sources accumulate in order."""
+        lists = [np.ascontiguousarray(x, dtype=np.int32).ravel() for x in (north, south, east, west)]
+        times = np.ascontiguousarray(table[0], dtype=np.float64).ravel()
+        vals = np.ascontiguousarray(table[1], dtype=np.float64).ravel()
+        if vals.size != times.size:
+            raise ValueError("the table needs one force per time")
+        args = []
+        for a in lists:
+            args += [ctypes.c_void_p(a.ctypes.data) if a.size else None, a.size]
+        call("afem_elastodynamics_set_double_couple", self.h, *args, ctypes.c_void_p(times.ctypes.data) if times.size
+             else None, ctypes.c_void_p(vals.ctypes.data) if vals.size else None, times.size, C.AFEM_MEM_HOST)

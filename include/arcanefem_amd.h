@@ -247,6 +247,38 @@ int afem_bsr_assemble_elasticity_p1_ex(afem_bsr* bsr, double lambda, double mu2,
 int afem_bsr_assemble_elastodynamics_p1(afem_bsr* bsr, const double c[11], const double* body_force, const double* u,
                                         const double* v, const double* a, const uint8_t* fixed, double* rhs,
                                         int rhs_mode);
+/* Paraxial (absorbing) boundary of modules/soildynamics/FemModule.cc on a
+ * block-2 triangle matrix: for every listed boundary edge (face_nodes[2
+ * n_faces], local node ids, in `mem`) of length L and unit normal n (only
+ * nx^2, ny^2 and nx ny enter, so the orientation does not matter)
+ *   values += the EDGE2 element matrix (:1376-1486, assembled :1540-1577):
+ *     k11 = p[0] (nx^2 cp + ny^2 cs), k22 = p[0] (ny^2 cp + nx^2 cs),
+ *     k12 = p[0] nx ny (cp - cs); for i, j in {a, b}, i an owned row:
+ *     k11 m_ij to (2i, 2j), k22 m_ij to (2i+1, 2j+1), m_ij = L/3 (i = j) or
+ *     L/6, and k12 L/6 to (2i, 2j+1) and (2i+1, 2j) -- on the diagonal block
+ *     too, as the reference's matrix has it (:1445-1483);
+ *   rhs   += the edge loop over U, V, A (:870-936): for an owned end v, with
+ *     S(W) = W_a + W_b + W_v per component,
+ *     rhs[2v]   += (p[0] f1(U) - p[1] f1(V) - p[2] f1(A)) L/6,
+ *       f1(W) = cp (nx^2 S1 + nx ny S2) + cs (ny^2 S1 - nx ny S2),
+ *     rhs[2v+1] likewise with
+ *       f2(W) = cp (nx ny S1 + ny^2 S2) + cs (-nx ny S1 + nx^2 S2),
+ *     unless the DoF is flagged in `fixed` (one byte per owned DoF, or NULL).
+ * p[3] (host) = the module's c7, c8, c9 (:297-299): rho gamma / (beta dt),
+ * rho (1 - gamma / beta), rho dt (1 - gamma / (2 beta)).  u, v, a: 2 doubles
+ * per LOCAL node (a ghost end's values are read); rhs: 2 per owned node; all
+ * device pointers.  The terms are added whether or not a DoF is constrained.
+ * An edge listed twice counts twice; an edge whose two ends are both ghosts
+ * is ignored (the module's isOwn() guards); an edge that is no edge of the
+ * mesh, or a node id out of range: AFEM_ERR_ARG.  One launch, one lane per
+ * owned boundary node; every value and RHS entry has one writer (no atomics,
+ * bitwise reproducible); the value positions come from a plan built from the
+ * face list and kept with the matrix until another list is given (no column
+ * search in the kernel).  Works on both value layouts.  Other (cell, NB_DOF)
+ * combinations: AFEM_ERR_NOT_IMPL. */
+int afem_bsr_add_paraxial_p1(afem_bsr* bsr, const int32_t* face_nodes, int64_t n_faces, int mem, double cp, double cs,
+                             const double p[3], const double* u, const double* v, const double* a, const uint8_t* fixed,
+                             double* rhs);
 int afem_bsr_reset_values(afem_bsr* bsr);                       /* resetMatrixValues */
 int afem_bsr_set_value(afem_bsr* bsr, int32_t row, int32_t col, double v); /* BSRMatrix::setValue */
 int afem_bsr_get_value(afem_bsr* bsr, int32_t row, int32_t col, double* v); /* BSRMatrix::getValue */
@@ -775,6 +807,43 @@ int afem_elastodynamics_set_traction(afem_elastodynamics* dyn, const int32_t* fa
  * each step (FemModule.cc:175, :189). */
 int afem_elastodynamics_set_traction_table(afem_elastodynamics* dyn, int traction_index, const double* times,
                                            const double* values, int64_t n);
+/* ---- modules/soildynamics on the 2D loop: the same block-2 TRIA3 step plus
+ * paraxial boundaries and a double-couple source.  Order within a step: the
+ * fused kernel, the paraxial launch (LHS + RHS), the tractions, the Dirichlet
+ * blocks, the double-couple assignment, the solve, the re-imposition, the
+ * Newmark update (FemModule.cc:454-480).  The LHS is re-assembled every step
+ * (the module assembles it once, :223-226: the same values), so
+ * afem_elastodynamics_set_time_step keeps working, and
+ * afem_elastodynamics_operators returns it with the paraxial terms in it.
+ * All three entries: a 3D handle gives AFEM_ERR_NOT_IMPL.  A handle without a
+ * paraxial block and without a source launches nothing new. */
+/* The material as wave speeds (:275-278): mu = cs^2 rho, lambda = cp^2 rho -
+ * 2 mu; replaces the values derived from E and nu.  The paraxial terms use cp
+ * and cs as given; with E, nu or afem_elastodynamics_set_lame they use cs =
+ * sqrt(mu / rho), cp = sqrt((lambda + 2 mu) / rho) (:261-273). */
+int afem_elastodynamics_set_wave_speeds(afem_elastodynamics* dyn, double cp, double cs);
+/* One paraxial-boundary-condition block: its boundary edges (face_nodes[2
+ * n_faces], local ids, in `mem`), the terms of afem_bsr_add_paraxial_p1 with
+ * the step's p7 .. p9.  Blocks accumulate (an edge in two blocks counts
+ * twice); all blocks of a handle run in one launch per step, from a plan
+ * built here.  A handle with etam or etak != 0 or scheme 1: AFEM_ERR_NOT_IMPL
+ * (the module's own FATAL, :321). */
+int afem_elastodynamics_set_paraxial(afem_elastodynamics* dyn, const int32_t* face_nodes, int64_t n_faces, int mem);
+/* One double-couple block, force based (:946-987; the only method the module
+ * implements): after everything else of the step's right-hand side
+ *   rhs[2 north] = F, rhs[2 south] = -F, rhs[2 east + 1] = -F, rhs[2 west + 1] = F
+ * is ASSIGNED on the listed nodes (local ids, in `mem`; a list may be empty;
+ * non-owned nodes ignored), F = the piecewise-linear interpolation of
+ * (times[n], values[n], host) at the step's time, constant outside -- the
+ * semantics of afem_elastodynamics_set_traction_table with one value per
+ * time.  Several sources accumulate and are applied in their order.  A handle
+ * with etam or etak != 0 or scheme 1: AFEM_ERR_NOT_IMPL.  A source DoF that a
+ * Dirichlet block constrains: AFEM_ERR_ARG from afem_elastodynamics_step
+ * (checked there because blocks may be registered in either order). */
+int afem_elastodynamics_set_double_couple(afem_elastodynamics* dyn, const int32_t* north, int64_t n_north,
+                                          const int32_t* south, int64_t n_south, const int32_t* east, int64_t n_east,
+                                          const int32_t* west, int64_t n_west, const double* times, const double* values,
+                                          int64_t n, int mem);
 /* Changes dt from the next step on (passmo shortens the step that would
  * overshoot the final time, modules/passmo/ElastodynamicModule.cc:525-530);
  * the Newmark coefficients follow and a reused multigrid hierarchy is rebuilt. */
@@ -797,7 +866,8 @@ int afem_elastodynamics_operators(afem_elastodynamics* dyn, afem_csr_view* lhs, 
 int afem_elastodynamics_profile(afem_elastodynamics* dyn, int on);
 typedef struct afem_step_timing {
   double assemble_ms;  /* fused block-3 re-assembly of c0 M + K + body force (2D: the fused step kernel, LHS + RHS) */
-  double rhs_ms;       /* RHS operators: lincombs + mass (and damping) SpMVs (2D: the tractions) */
+  double rhs_ms;       /* RHS operators: lincombs + mass (and damping) SpMVs (2D: the paraxial launch, the
+                          tractions and the double-couple assignment) */
   double bc_ms;        /* penalty lists + the Newmark predictor (the warm start) */
   double solve_ms;     /* the PCG (setup of a new multigrid hierarchy included) */
   double precond_ms;   /* part of solve_ms: the preconditioner applications */
