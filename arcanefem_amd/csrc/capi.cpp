@@ -11,6 +11,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include "afem_internal.hpp"
+#include "elastodynamics.hpp"
 
 using namespace afem;
 
@@ -1659,7 +1660,7 @@ int afem_elastodynamics_operators(afem_elastodynamics* h, afem_csr_view* lhs, co
   }
   if (scalar_rows) *scalar_rows = d->K.csr_rows.p;
   if (scalar_cols) *scalar_cols = d->K.csr_cols.p;
-  if (mass_values) *mass_values = d->mvals.p;
+  if (mass_values) *mass_values = d->tet.mvals.p;
   if (c)
     for (int i = 0; i < 11; ++i) c[i] = d->c[i];
   API_END

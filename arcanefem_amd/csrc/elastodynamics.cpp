@@ -18,7 +18,8 @@
 // same structure, assembled once.
 //
 // The module's own case, 2D TRIA3 with block 2, runs through the same handle
-// (nb = 2, dyn_create_tri / dyn_step_tri): one fused kernel per step writes
+// and the same dyn_create / dyn_step (nb = 2; the phases that differ are the
+// *_tet / *_tri functions): one fused kernel per step writes
 // the LHS and the complete RHS from U, V, A (assemble_elastodynamics_tri), so
 // that path keeps no M / K_lambda / K_mu and runs no SpMV or lincomb for the
 // RHS; tractions (:880-967, constant or a CaseTable), the vectorial Dirichlet
@@ -38,7 +39,7 @@
 #include <map>
 #include <vector>
 
-#include "afem_internal.hpp"
+#include "elastodynamics.hpp"
 
 namespace afem {
 
@@ -60,19 +61,45 @@ struct ProfileCommGuard {
   ProfileCommGuard& operator=(const ProfileCommGuard&) = delete;
 };
 
-// CaseTable::CurveLinear with one value per time: piecewise linear, constant outside
-double table_interp1(const std::vector<double>& times, const std::vector<double>& values, double t)
+template <class T>
+std::vector<T> to_host(Ctx& ctx, const T* p, int64_t n, int mem)
 {
-  const size_t n = times.size();
-  if (t <= times.front() || n == 1) return values[0];
-  if (t >= times.back()) return values[n - 1];
-  const size_t k = std::upper_bound(times.begin(), times.end(), t) - times.begin();  // times[k-1] <= t < times[k]
-  const double w = (t - times[k - 1]) / (times[k] - times[k - 1]);
-  return values[k - 1] + w * (values[k] - values[k - 1]);
+  std::vector<T> h(n);
+  if (n) {
+    AFEM_HIP(hipMemcpyAsync(h.data(), p, n * sizeof(T), mem == AFEM_MEM_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost,
+                            ctx.stream));
+    ctx.sync();
+  }
+  return h;
 }
 
-void halo_for(LinearSystem& ls, Comm* comm, Mesh& m)
+template <class T>
+void upload(Ctx& ctx, DevBuf<T>& b, const std::vector<T>& h)
 {
+  b.alloc(h.size());
+  if (!h.empty()) AFEM_HIP(hipMemcpyAsync(b.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, ctx.stream));
+  ctx.sync();
+}
+
+// CaseTable::CurveLinear with `width` values per time: piecewise linear, constant outside
+void table_interp(const std::vector<double>& times, const std::vector<double>& values, int width, double t, double* out)
+{
+  const size_t n = times.size();
+  const bool before = t <= times.front() || n == 1;
+  if (before || t >= times.back()) {
+    for (int i = 0; i < width; ++i) out[i] = values[width * (before ? 0 : n - 1) + i];
+    return;
+  }
+  const size_t k = std::upper_bound(times.begin(), times.end(), t) - times.begin();  // times[k-1] <= t < times[k]
+  const double w = (t - times[k - 1]) / (times[k] - times[k - 1]);
+  for (int i = 0; i < width; ++i)
+    out[i] = values[width * (k - 1) + i] + w * (values[width * k + i] - values[width * (k - 1) + i]);
+}
+
+void halo_for(LinearSystem& ls, const Elastodynamics* d)
+{
+  Comm* comm = d->comm;
+  Mesh& m = *d->mesh;
   if (!comm || comm_nranks(comm) == 1) return;
   std::vector<int> nb;
   std::vector<int64_t> sc, rc;
@@ -90,7 +117,7 @@ void halo_for(LinearSystem& ls, Comm* comm, Mesh& m)
                  "afem_mesh_create_subdomain)");
     structured_halo_lists(m.st.dim, m.st.n, m.st.nz, m.st.nranks, m.st.rank, nb, sc, rc, si, ri);
   }
-  expand_dof_lists(3, sc, rc, si, ri);
+  expand_dof_lists(d->nb, sc, rc, si, ri);
   std::vector<int32_t> nb32(nb.begin(), nb.end());
   ls.halo.reset(new Halo());
   halo_setup(*ls.halo, *ls.ctx, comm, (int)nb.size(), nb32.data(), sc.data(), si.data(), rc.data(), ri.data());
@@ -120,6 +147,28 @@ void init_ls(LinearSystem& ls, Ctx* ctx, int64_t n, int64_t n_cols)
   AFEM_HIP(hipMemsetAsync(ls.sol.p, 0, n_cols * sizeof(double), ctx->stream));
   AFEM_HIP(hipMemsetAsync(ls.forced_info.p, 0, n, ctx->stream));
   AFEM_HIP(hipMemsetAsync(ls.elim_info.p, 0, n, ctx->stream));
+}
+
+// the scalar CSR of K's structure (bsr_expand_scalar) with `values` on it as l's matrix
+void attach_csr(LinearSystem& l, const Bsr& K, double* values)
+{
+  const int k = K.nb_dof;
+  l.has_csr = true;
+  l.csr_n = l.n_rows;
+  l.csr_nnz = K.s.nnz * k * k;
+  l.csr_rows = K.csr_rows.p;
+  l.csr_diag = nullptr;
+  l.csr_cols = K.csr_cols.p;
+  l.csr_vals = values;
+  l.blk_k = k;
+  l.blk_n = K.s.n_rows;
+  l.blk_rows = K.s.row_ptr.p;
+  l.blk_cols = K.s.cols.p;
+}
+
+void require_2d(const Elastodynamics* d, const char* what)
+{
+  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, (std::string(what) + ": the 2D loop's entry").c_str());
 }
 }  // namespace
 
@@ -166,212 +215,20 @@ void dyn_coefficients(Elastodynamics* d)
   }
 }
 
-namespace {
-Elastodynamics* dyn_create_tri(Mesh* mesh, Comm* comm, const afem_newmark_params* prm, const int32_t* fixed_nodes,
-                               int64_t n_fixed, int mem)
-{
-  AFEM_REQUIRE(prm->dt > 0 && prm->E > 0 && prm->nu > -1.0 && prm->nu < 0.5 && prm->rho >= 0, AFEM_ERR_ARG,
-               "elastodynamics: bad material or time step");
-  AFEM_REQUIRE(n_fixed == 0 || fixed_nodes, AFEM_ERR_ARG, "fixed_nodes is NULL");
-  AFEM_REQUIRE(prm->scheme == 0 || prm->scheme == 1, AFEM_ERR_ARG,
-               "elastodynamics: scheme 0 (Newmark-beta) or 1 (generalized-alpha)");
-  AFEM_REQUIRE(!comm || comm_nranks(comm) == 1, AFEM_ERR_NOT_IMPL,
-               "2D elastodynamics runs on one subdomain (a communicator of more than one rank)");
-  AFEM_REQUIRE(mesh->n_own == mesh->n_nodes, AFEM_ERR_NOT_IMPL,
-               "2D elastodynamics runs on one subdomain (the mesh has ghost nodes)");
-  mesh->ctx->set_device();
-  auto* d = new Elastodynamics();
-  try {
-    Ctx& ctx = *mesh->ctx;
-    d->mesh = mesh;
-    d->ctx = &ctx;
-    d->comm = comm;
-    d->p = *prm;
-    d->nb = 2;
-    if (!(d->p.penalty > 0)) d->p.penalty = 1.0e30;
-    d->mu2 = (prm->E / (2 * (1 + prm->nu))) * 2;  // FemModule.cc:239-240; afem_elastodynamics_set_lame: :242-246
-    d->lambda = prm->E * prm->nu / ((1 + prm->nu) * (1 - 2 * prm->nu));
-    dyn_coefficients(d);
-    d->damped = prm->etak != 0.0 || (prm->scheme == 1 && prm->alpf != 0.0);
-    d->t = prm->dt;
-    d->n = 2 * mesh->n_own;
-    d->n_cols = 2 * mesh->n_nodes;
-    d->K.mesh = mesh;
-    d->K.nb_dof = 2;
-    d->K.order_per_block = false;  // CSR row order: the values are the linear system's matrix
-    build_structure(*mesh, d->K.s, 2);
-    d->K.values.alloc((size_t)d->K.s.nnz * 4);
-    AFEM_HIP(hipMemsetAsync(d->K.values.p, 0, d->K.values.bytes(), ctx.stream));
-    d->K.has_sparsity = true;
-    bsr_expand_scalar(d->K, nullptr);
-    init_ls(d->ls, &ctx, d->n, d->n_cols);
-    LinearSystem& l = d->ls;
-    l.has_csr = true;
-    l.csr_n = d->n;
-    l.csr_nnz = d->K.s.nnz * 4;
-    l.csr_rows = d->K.csr_rows.p;
-    l.csr_diag = nullptr;
-    l.csr_cols = d->K.csr_cols.p;
-    l.csr_vals = d->K.values.p;
-    l.blk_k = 2;
-    l.blk_n = d->K.s.n_rows;
-    l.blk_rows = d->K.s.row_ptr.p;
-    l.blk_cols = d->K.s.cols.p;
-    for (auto* b : { &d->U, &d->V, &d->A }) {
-      b->alloc(d->n_cols);
-      AFEM_HIP(hipMemsetAsync(b->p, 0, b->bytes(), ctx.stream));
-    }
-    d->fixed2.alloc(d->n);
-    AFEM_HIP(hipMemsetAsync(d->fixed2.p, 0, d->fixed2.bytes(), ctx.stream));
-    ctx.sync();
-    if (n_fixed) {  // the clamped nodes of the 3D entry: both components 0, by penalty
-      const double zero[2] = { 0.0, 0.0 };
-      dyn_set_dirichlet_vectorial(d, fixed_nodes, n_fixed, zero, 3u, AFEM_DIRICHLET_PENALTY, mem);
-    }
-  }
-  catch (...) {
-    delete d;
-    throw;
-  }
-  return d;
-}
-
-void dyn_step_tri(Elastodynamics* d, afem_solve_stats* st)
-{
-  Ctx& ctx = *d->ctx;
-  ctx.set_device();
-  const bool prof = d->profile;
-  auto mark = [&](int i) {
-    if (prof) AFEM_HIP(hipEventRecord(d->ev[i], ctx.stream));
-  };
-  // a double-couple DoF that a Dirichlet block constrains: the assignment would undo the condition's RHS
-  for (const auto& dc : d->dc2)
-    for (int32_t dof : dc.hdofs)
-      AFEM_REQUIRE(!d->dir_dofs.count(dof), AFEM_ERR_ARG,
-                   "elastodynamics step: a double-couple DoF is constrained by a Dirichlet condition");
-  ProfileCommGuard prof_guard(d->ls.opts, prof);
-  mark(0);
-  // LHS c0 M + K(c1, c2) and the whole RHS of :645-867 in one pass (set mode)
-  const double f[2] = { d->p.body_force[0], d->p.body_force[1] };
-  assemble_elastodynamics_tri(d->K, d->c, f, d->U.p, d->V.p, d->A.p, d->fixed2.p, d->ls.rhs.p, 0);
-  mark(1);
-  // paraxial boundaries (modules/soildynamics/FemModule.cc): the EDGE2 matrix added to the LHS
-  // (:1376-1486) and the edge loop over U, V, A to the RHS (:870-936), all blocks in one launch
-  if (d->par.n) {
-    const double rho = d->p.rho, dt = d->p.dt, gamma = d->gamma, beta = d->beta;
-    // the module's c7 .. c9 (:297-299) -- not the fused kernel's damping terms c[7 .. 10], zero here
-    const double p[3] = { rho * gamma / beta / dt, rho * (1. - gamma / beta), rho * dt * (1. - gamma / (2. * beta)) };
-    const double mu = 0.5 * d->mu2;  // wave speeds of E, nu or lambda, mu (:261-273) unless given (:275-278)
-    const double cs = d->cs > 0 ? d->cs : std::sqrt(mu / rho);
-    const double cp = d->cp > 0 ? d->cp : std::sqrt((d->lambda + 2. * mu) / rho);
-    paraxial_add(ctx, d->par, cp, cs, p, d->U.p, d->V.p, d->A.p, d->fixed2.p, d->K.values.p, d->ls.rhs.p);
-  }
-  // tractions t_i |e| / 2 per face node on the unfixed DoFs (:880-967), at the step's time for a table
-  for (const auto& tr : d->trac2) {
-    double t[2] = { tr.t[0], tr.t[1] };
-    if (!tr.times.empty()) table_interp2(tr.times, tr.values, d->t, t);
-    traction2_add(ctx, (int64_t)tr.nodes.n, tr.nodes.p, tr.w.p, t, tr.mask, d->fixed2.p, d->ls.rhs.p);
-  }
-  mark(2);
-  // the deck's Dirichlet blocks in their order: later ones override earlier ones per DoF
-  for (const auto& dc : d->dir2)
-    ls_set_vectorial(d->ls, 2, dc.nodes.p, (int64_t)dc.nodes.n, AFEM_MEM_DEVICE, d->dir_method, dc.v, dc.mask,
-                     d->p.penalty);
-  // warm start from the Newmark predictor, as in 3D
-  vec_lincomb(ctx, d->n, 1.0, d->U.p, d->p.dt, d->V.p, d->p.dt * d->p.dt * (0.5 - d->beta), d->A.p, d->ls.sol.p);
-  d->ls.opts.initial_guess = 1;
-  // double couple (modules/soildynamics/FemModule.cc:946-987): after everything else the listed DoFs'
-  // RHS entries are ASSIGNED +-F, F = the source's table at the step's time
-  const bool prof_dc = prof && !d->dc2.empty();  // timed apart: it belongs to rhs_ms, not to bc_ms
-  if (prof_dc) AFEM_HIP(hipEventRecord(d->ev_dc[0], ctx.stream));
-  for (const auto& dc : d->dc2) {
-    const double F = table_interp1(dc.times, dc.values, d->t);
-    vec_scatter_scaled(ctx, (int64_t)dc.dofs.n, dc.dofs.p, dc.sign.p, F, d->ls.rhs.p);
-  }
-  if (prof_dc) AFEM_HIP(hipEventRecord(d->ev_dc[1], ctx.stream));
-  mark(3);
-  ls_solve(d->ls, &d->last);
-  prof_guard.restore();
-  mark(4);
-  // the constrained values re-imposed on the solution (_solve, :1416-1417)
-  if (d->imp_ids.n) vec_scatter(ctx, (int64_t)d->imp_ids.n, d->imp_ids.p, d->imp_vals.p, d->ls.sol.p);
-  newmark_update(ctx, d->n, d->p.dt, d->beta, d->gamma, d->ls.sol.p, d->U.p, d->V.p, d->A.p);
-  mark(5);
-  ctx.sync();
-  d->t += d->p.dt;  // _updateTime, :189
-  if (prof) {
-    float ms[5] = {};
-    for (int i = 0; i < 5; ++i) AFEM_HIP(hipEventElapsedTime(&ms[i], d->ev[i], d->ev[i + 1]));
-    float tot = 0.f;
-    AFEM_HIP(hipEventElapsedTime(&tot, d->ev[0], d->ev[5]));
-    afem_step_timing& t = d->timing;
-    float dc_ms = 0.f;
-    if (prof_dc) AFEM_HIP(hipEventElapsedTime(&dc_ms, d->ev_dc[0], d->ev_dc[1]));
-    t.assemble_ms = ms[0];
-    t.rhs_ms = ms[1] + dc_ms;  // the paraxial launch, the tractions and the double-couple assignment
-    t.bc_ms = ms[2] - dc_ms;
-    t.solve_ms = ms[3];
-    t.precond_ms = d->last.precond_ms;
-    t.update_ms = ms[4];
-    t.total_ms = tot;
-    t.iterations = d->last.iterations;
-  }
-  if (st) *st = d->last;
-}
-
-template <class T>
-std::vector<T> to_host(Ctx& ctx, const T* p, int64_t n, int mem)
-{
-  std::vector<T> h(n);
-  if (n) {
-    AFEM_HIP(hipMemcpyAsync(h.data(), p, n * sizeof(T), mem == AFEM_MEM_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost,
-                            ctx.stream));
-    ctx.sync();
-  }
-  return h;
-}
-
-template <class T>
-void upload(Ctx& ctx, DevBuf<T>& b, const std::vector<T>& h)
-{
-  b.alloc(h.size());
-  if (!h.empty()) AFEM_HIP(hipMemcpyAsync(b.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, ctx.stream));
-  ctx.sync();
-}
-}  // namespace
-
-void table_interp2(const std::vector<double>& times, const std::vector<double>& values, double t, double out[2])
-{
-  const size_t n = times.size();
-  if (t <= times.front() || n == 1) {
-    out[0] = values[0];
-    out[1] = values[1];
-    return;
-  }
-  if (t >= times.back()) {
-    out[0] = values[2 * n - 2];
-    out[1] = values[2 * n - 1];
-    return;
-  }
-  const size_t k = std::upper_bound(times.begin(), times.end(), t) - times.begin();  // times[k-1] <= t < times[k]
-  const double w = (t - times[k - 1]) / (times[k] - times[k - 1]);
-  for (int i = 0; i < 2; ++i) out[i] = values[2 * (k - 1) + i] + w * (values[2 * k + i] - values[2 * (k - 1) + i]);
-}
-
 void dyn_set_lame(Elastodynamics* d, double lambda, double mu)
 {
-  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, "afem_elastodynamics_set_lame: the 2D loop's entry");
+  require_2d(d, "afem_elastodynamics_set_lame");
   AFEM_REQUIRE(mu > 0 && lambda + mu > 0, AFEM_ERR_ARG, "afem_elastodynamics_set_lame: bad Lame parameters");
   d->lambda = lambda;
   d->mu2 = 2 * mu;
-  d->cp = d->cs = 0.0;  // the paraxial wave speeds follow the Lame parameters again (FemModule.cc:268-273)
+  d->tri.cp = d->tri.cs = 0.0;  // the paraxial wave speeds follow the Lame parameters again (FemModule.cc:268-273)
   dyn_coefficients(d);
 }
 
 void dyn_set_dirichlet_vectorial(Elastodynamics* d, const int32_t* nodes, int64_t n, const double values[2],
                                  unsigned mask, int method, int mem)
 {
-  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, "afem_elastodynamics_set_dirichlet_vectorial: the 2D loop's entry");
+  require_2d(d, "afem_elastodynamics_set_dirichlet_vectorial");
   AFEM_REQUIRE(n >= 0 && (n == 0 || nodes) && values, AFEM_ERR_ARG,
                "afem_elastodynamics_set_dirichlet_vectorial: bad node list or values");
   AFEM_REQUIRE(method == AFEM_DIRICHLET_PENALTY || method == AFEM_DIRICHLET_ROW_ELIMINATION ||
@@ -379,7 +236,7 @@ void dyn_set_dirichlet_vectorial(Elastodynamics* d, const int32_t* nodes, int64_
                AFEM_ERR_NOT_IMPL,
                "enforce-Dirichlet-method: Penalty, RowElimination or RowColumnElimination (WeakPenalty is not "
                "implemented)");
-  AFEM_REQUIRE(d->dir_method < 0 || d->dir_method == method, AFEM_ERR_ARG,
+  AFEM_REQUIRE(d->tri.dir_method < 0 || d->tri.dir_method == method, AFEM_ERR_ARG,
                "one enforce-Dirichlet-method for all conditions of a run");
   mask &= 3u;
   if (n == 0 || !mask) return;
@@ -391,25 +248,25 @@ void dyn_set_dirichlet_vectorial(Elastodynamics* d, const int32_t* nodes, int64_
     AFEM_REQUIRE(v >= 0 && v < d->mesh->n_nodes, AFEM_ERR_ARG, "Dirichlet node id out of range");
     if (v < d->mesh->n_own) own.push_back(v);
   }
-  d->dir_method = method;
-  Elastodynamics::Dirichlet2 dc;
+  d->tri.dir_method = method;
+  Elastodynamics::Tri::Dirichlet2 dc;
   upload(ctx, dc.nodes, own);
   dc.mask = mask;
   for (int i = 0; i < 2; ++i) dc.v[i] = (mask >> i) & 1u ? values[i] : 0.0;
   for (int32_t v : own)
     for (int i = 0; i < 2; ++i)
-      if ((mask >> i) & 1u) d->dir_dofs[2 * v + i] = values[i];
-  d->dir2.push_back(std::move(dc));
+      if ((mask >> i) & 1u) d->tri.dir_dofs[2 * v + i] = values[i];
+  d->tri.dir2.push_back(std::move(dc));
   // the flags of the kernel's and the tractions' guards, and the list re-imposed after the solve
   std::vector<uint8_t> flags(d->n, 0);
   std::vector<int32_t> ids;
   std::vector<double> vals;
-  for (const auto& kv : d->dir_dofs) {
+  for (const auto& kv : d->tri.dir_dofs) {
     flags[kv.first] = 1;
     ids.push_back(kv.first);
     vals.push_back(kv.second);
   }
-  upload(ctx, d->fixed2, flags);
+  upload(ctx, d->tri.fixed2, flags);
   upload(ctx, d->imp_ids, ids);
   upload(ctx, d->imp_vals, vals);
 }
@@ -417,7 +274,7 @@ void dyn_set_dirichlet_vectorial(Elastodynamics* d, const int32_t* nodes, int64_
 void dyn_set_traction(Elastodynamics* d, const int32_t* face_nodes, int64_t n_faces, const double t[2], unsigned mask,
                       int mem)
 {
-  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, "afem_elastodynamics_set_traction: the 2D loop's entry");
+  require_2d(d, "afem_elastodynamics_set_traction");
   AFEM_REQUIRE(n_faces >= 0 && (n_faces == 0 || face_nodes) && t, AFEM_ERR_ARG,
                "afem_elastodynamics_set_traction: bad face list or traction");
   Ctx& ctx = *d->ctx;
@@ -439,23 +296,23 @@ void dyn_set_traction(Elastodynamics* d, const int32_t* face_nodes, int64_t n_fa
     nodes.push_back(kv.first);
     ws.push_back(kv.second);
   }
-  Elastodynamics::Traction2 tr;
+  Elastodynamics::Tri::Traction2 tr;
   upload(ctx, tr.nodes, nodes);
   upload(ctx, tr.w, ws);
   tr.mask = mask & 3u;
   for (int i = 0; i < 2; ++i) tr.t[i] = (tr.mask >> i) & 1u ? t[i] : 0.0;
-  d->trac2.push_back(std::move(tr));
+  d->tri.trac2.push_back(std::move(tr));
 }
 
 void dyn_set_traction_table(Elastodynamics* d, int index, const double* times, const double* values, int64_t n)
 {
-  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, "afem_elastodynamics_set_traction_table: the 2D loop's entry");
-  AFEM_REQUIRE(index >= 0 && index < (int)d->trac2.size(), AFEM_ERR_ARG,
+  require_2d(d, "afem_elastodynamics_set_traction_table");
+  AFEM_REQUIRE(index >= 0 && index < (int)d->tri.trac2.size(), AFEM_ERR_ARG,
                "afem_elastodynamics_set_traction_table: no such traction");
   AFEM_REQUIRE(n >= 1 && times && values, AFEM_ERR_ARG, "afem_elastodynamics_set_traction_table: empty table");
   for (int64_t i = 1; i < n; ++i)
     AFEM_REQUIRE(times[i] > times[i - 1], AFEM_ERR_ARG, "afem_elastodynamics_set_traction_table: times must increase");
-  auto& tr = d->trac2[index];
+  auto& tr = d->tri.trac2[index];
   tr.times.assign(times, times + n);
   tr.values.assign(values, values + 2 * n);
 }
@@ -529,7 +386,7 @@ namespace {
 // the module's own FATAL (:321) and what the paraxial constants are derived for
 void require_soil(const Elastodynamics* d, const char* what)
 {
-  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, (std::string(what) + ": the 2D loop's entry").c_str());
+  require_2d(d, what);
   AFEM_REQUIRE(d->p.scheme == 0 && d->p.etam == 0.0 && d->p.etak == 0.0, AFEM_ERR_NOT_IMPL,
                (std::string(what) + ": Only Newmark-beta works for time-discretization (no damping, no generalized-alpha)")
                    .c_str());
@@ -538,14 +395,14 @@ void require_soil(const Elastodynamics* d, const char* what)
 
 void dyn_set_wave_speeds(Elastodynamics* d, double cp, double cs)
 {
-  AFEM_REQUIRE(d->nb == 2, AFEM_ERR_NOT_IMPL, "afem_elastodynamics_set_wave_speeds: the 2D loop's entry");
+  require_2d(d, "afem_elastodynamics_set_wave_speeds");
   AFEM_REQUIRE(d->p.rho > 0, AFEM_ERR_ARG, "afem_elastodynamics_set_wave_speeds: rho must be > 0");
   const double mu = cs * cs * d->p.rho, lambda = cp * cp * d->p.rho - 2 * mu;  // FemModule.cc:275-278
   AFEM_REQUIRE(cp > 0 && cs > 0 && lambda + mu > 0, AFEM_ERR_ARG, "afem_elastodynamics_set_wave_speeds: bad wave speeds");
   d->lambda = lambda;
   d->mu2 = 2 * mu;
-  d->cp = cp;
-  d->cs = cs;
+  d->tri.cp = cp;
+  d->tri.cs = cs;
   dyn_coefficients(d);
 }
 
@@ -558,12 +415,12 @@ void dyn_set_paraxial(Elastodynamics* d, const int32_t* face_nodes, int64_t n_fa
   Ctx& ctx = *d->ctx;
   ctx.set_device();
   const std::vector<int32_t> fn = to_host(ctx, face_nodes, 2 * n_faces, mem);
-  std::vector<int32_t> all = d->par_faces;
+  std::vector<int32_t> all = d->tri.par_faces;
   all.insert(all.end(), fn.begin(), fn.end());
   ParaxialPlan plan;
   paraxial_plan_build(d->K, all, plan);  // throws before the handle changes
-  d->par = std::move(plan);
-  d->par_faces = std::move(all);
+  d->tri.par = std::move(plan);
+  d->tri.par_faces = std::move(all);
 }
 
 void dyn_set_double_couple(Elastodynamics* d, const int32_t* const nodes[4], const int64_t n_nodes[4], const double* times,
@@ -588,7 +445,7 @@ void dyn_set_double_couple(Elastodynamics* d, const int32_t* const nodes[4], con
       if (v < d->mesh->n_own) m[2 * v + comp[g]] = sgn[g];
     }
   }
-  Elastodynamics::DoubleCouple2 dc;
+  Elastodynamics::Tri::DoubleCouple2 dc;
   std::vector<double> s;
   for (const auto& kv : m) {
     dc.hdofs.push_back(kv.first);
@@ -598,206 +455,302 @@ void dyn_set_double_couple(Elastodynamics* d, const int32_t* const nodes[4], con
   upload(ctx, dc.sign, s);
   dc.times.assign(times, times + n);
   dc.values.assign(values, values + n);
-  d->dc2.push_back(std::move(dc));
+  d->tri.dc2.push_back(std::move(dc));
 }
+
+// ---------------------------------------------------------------- create
+namespace {
+// the mass and damping operators on K's structure, the multigrid hints, the halos and the clamped DoFs
+void create_tet(Elastodynamics* d, const int32_t* fixed_nodes, int64_t n_fixed, int mem)
+{
+  Ctx& ctx = *d->ctx;
+  Mesh* mesh = d->mesh;
+  Elastodynamics::Tet& s = d->tet;
+  // an operator of the RHS: its values assembled once through K, its SpMV's system on K's scalar CSR
+  auto op = [&](LinearSystem& l, DevBuf<double>& vals, double lambda, double mu2, double c0) {
+    vals.alloc((size_t)d->K.s.nnz * 9);
+    std::swap(d->K.values, vals);
+    assemble_elasticity_tet(d->K, lambda, mu2, c0, nullptr, nullptr, 0);
+    std::swap(d->K.values, vals);
+    init_ls(l, &ctx, d->n, d->n_cols);
+    attach_csr(l, d->K, vals.p);
+    halo_for(l, d);
+  };
+  op(s.lsm, s.mvals, 0.0, 0.0, 1.0);  // M (c0 = 1)
+  if (d->damped) {                    // the RHS's stiffness operators K(lambda = 1) and K(2 mu = 1)
+    op(s.lsl, s.klvals, 1.0, 0.0, 0.0);
+    op(s.lsu, s.kmvals, 0.0, 1.0, 0.0);
+  }
+  halo_for(d->ls, d);
+  // structured box (or z-slab: block-Jacobi V-cycles over the ranks): the multigrid preconditioner
+  const StructuredInfo& st = mesh->st;
+  if (st.valid && st.dim == 3 && !mesh->part.valid) {
+    d->ls.mg_k = 3;
+    d->ls.mg_nx = st.n;
+    d->ls.mg_nz = (st.k1 - st.k0) - 1;
+    d->ls.mg_multi = st.nranks > 1;
+    d->ls.mg_nzg = st.nz;
+    d->ls.mg_k0 = st.k0;
+    d->ls.mg_glo = st.ghost_lo >= 0;
+  }
+  s.MW.alloc(d->n);
+  AFEM_HIP(hipMemsetAsync(s.MW.p, 0, s.MW.bytes(), ctx.stream));
+  s.W.alloc(d->n_cols);  // ghost part filled by the mass SpMV's halo exchange
+  AFEM_HIP(hipMemsetAsync(s.W.p, 0, s.W.bytes(), ctx.stream));
+  std::vector<int32_t> dofs;
+  for (int32_t nd : to_host(ctx, fixed_nodes, n_fixed, mem)) {
+    AFEM_REQUIRE(nd >= 0 && nd < mesh->n_nodes, AFEM_ERR_ARG, "fixed node id out of range");
+    if (nd < mesh->n_own)
+      for (int i = 0; i < 3; ++i) dofs.push_back(3 * nd + i);
+  }
+  upload(ctx, s.fixed, dofs);
+}
+
+void create_tri(Elastodynamics* d, const int32_t* fixed_nodes, int64_t n_fixed, int mem)
+{
+  Ctx& ctx = *d->ctx;
+  AFEM_HIP(hipMemsetAsync(d->K.values.p, 0, d->K.values.bytes(), ctx.stream));
+  d->tri.t = d->p.dt;
+  d->tri.fixed2.alloc(d->n);
+  AFEM_HIP(hipMemsetAsync(d->tri.fixed2.p, 0, d->tri.fixed2.bytes(), ctx.stream));
+  ctx.sync();
+  if (n_fixed) {  // the clamped nodes of the 3D entry: both components 0, by penalty
+    const double zero[2] = { 0.0, 0.0 };
+    dyn_set_dirichlet_vectorial(d, fixed_nodes, n_fixed, zero, 3u, AFEM_DIRICHLET_PENALTY, mem);
+  }
+}
+}  // namespace
 
 Elastodynamics* dyn_create(Mesh* mesh, Comm* comm, const afem_newmark_params* prm, const int32_t* fixed_nodes,
                            int64_t n_fixed, int mem)
 {
-  if (mesh->nv == 3 && mesh->dim == 2) return dyn_create_tri(mesh, comm, prm, fixed_nodes, n_fixed, mem);
-  {
-    AFEM_REQUIRE(mesh->nv == 4 && mesh->dim == 3, AFEM_ERR_NOT_IMPL,
-                 "elastodynamics needs a tetrahedral (3D) or a triangle (2D) mesh");
-    AFEM_REQUIRE(prm->dt > 0 && prm->E > 0 && prm->nu > -1.0 && prm->nu < 0.5 && prm->rho >= 0, AFEM_ERR_ARG,
-                 "elastodynamics: bad material or time step");
-    AFEM_REQUIRE(n_fixed == 0 || fixed_nodes, AFEM_ERR_ARG, "fixed_nodes is NULL");
-    AFEM_REQUIRE(prm->scheme == 0 || prm->scheme == 1, AFEM_ERR_ARG,
-                 "elastodynamics: scheme 0 (Newmark-beta) or 1 (generalized-alpha)");
-    if (comm)
-      AFEM_REQUIRE(comm_nranks(comm) == 1 ||
-                       (mesh->st.valid && mesh->st.nranks == comm_nranks(comm) && mesh->st.rank == comm_rank(comm)) ||
-                       (mesh->part.valid && mesh->part.nranks == comm_nranks(comm) &&
-                        mesh->part.rank == comm_rank(comm)),
-                   AFEM_ERR_ARG, "the mesh's slab / subdomain rank and nranks differ from the communicator");
-    mesh->ctx->set_device();
-    auto* d = new Elastodynamics();
-    try {
-      Ctx& ctx = *mesh->ctx;
-      d->mesh = mesh;
-      d->ctx = &ctx;
-      d->comm = comm;
-      d->p = *prm;
-      if (!(d->p.penalty > 0)) d->p.penalty = 1.0e30;  // modules/elasticity/Fem.axl:37-41
-      // modules/elastodynamics/FemModule.cc:130-134 (Lame) and :255-290 (time scheme)
-      d->mu2 = (prm->E / (2 * (1 + prm->nu))) * 2;
-      d->lambda = prm->E * prm->nu / ((1 + prm->nu) * (1 - 2 * prm->nu));
-      dyn_coefficients(d);
-      d->damped = prm->etak != 0.0 || (prm->scheme == 1 && prm->alpf != 0.0);
-      d->n = 3 * mesh->n_own;
-      d->n_cols = 3 * mesh->n_nodes;
-      // structure once; stiffness and mass share it
-      d->K.mesh = mesh;
-      d->K.nb_dof = 3;
-      d->K.order_per_block = false;
-      build_structure(*mesh, d->K.s);
-      d->K.values.alloc((size_t)d->K.s.nnz * 9);
-      d->K.has_sparsity = true;
-      d->mvals.alloc((size_t)d->K.s.nnz * 9);
-      std::swap(d->K.values, d->mvals);
-      assemble_elasticity_tet(d->K, 0.0, 0.0, 1.0, nullptr, nullptr, 0);  // M (c0 = 1)
-      std::swap(d->K.values, d->mvals);
-      if (d->damped) {  // the RHS's stiffness operators K(lambda = 1) and K(2 mu = 1)
-        d->klvals.alloc((size_t)d->K.s.nnz * 9);
-        d->kmvals.alloc((size_t)d->K.s.nnz * 9);
-        std::swap(d->K.values, d->klvals);
-        assemble_elasticity_tet(d->K, 1.0, 0.0, 0.0, nullptr, nullptr, 0);
-        std::swap(d->K.values, d->klvals);
-        std::swap(d->K.values, d->kmvals);
-        assemble_elasticity_tet(d->K, 0.0, 1.0, 0.0, nullptr, nullptr, 0);
-        std::swap(d->K.values, d->kmvals);
-      }
-      bsr_expand_scalar(d->K, nullptr);  // scalar rows / columns of the block-3 CSR (shared)
-      init_ls(d->ls, &ctx, d->n, d->n_cols);
-      init_ls(d->lsm, &ctx, d->n, d->n_cols);
-      if (d->damped) {
-        init_ls(d->lsl, &ctx, d->n, d->n_cols);
-        init_ls(d->lsu, &ctx, d->n, d->n_cols);
-      }
-      for (LinearSystem* l : { &d->ls, &d->lsm, &d->lsl, &d->lsu }) {
-        if (!l->ctx) continue;  // lsl / lsu without damping
-        l->has_csr = true;
-        l->csr_n = d->n;
-        l->csr_nnz = d->K.s.nnz * 9;
-        l->csr_rows = d->K.csr_rows.p;
-        l->csr_diag = nullptr;
-        l->csr_cols = d->K.csr_cols.p;
-        l->blk_k = 3;
-        l->blk_n = d->K.s.n_rows;
-        l->blk_rows = d->K.s.row_ptr.p;
-        l->blk_cols = d->K.s.cols.p;
-      }
-      {  // structured box (or z-slab: block-Jacobi V-cycles over the ranks): the multigrid preconditioner
-        const StructuredInfo& st = mesh->st;
-        if (st.valid && st.dim == 3 && !mesh->part.valid) {
-          d->ls.mg_k = 3;
-          d->ls.mg_nx = st.n;
-          d->ls.mg_nz = (st.k1 - st.k0) - 1;
-          d->ls.mg_multi = st.nranks > 1;
-          d->ls.mg_nzg = st.nz;
-          d->ls.mg_k0 = st.k0;
-          d->ls.mg_glo = st.ghost_lo >= 0;
-        }
-      }
-      d->ls.csr_vals = d->K.values.p;
-      d->lsm.csr_vals = d->mvals.p;
-      halo_for(d->ls, d->comm, *mesh);
-      halo_for(d->lsm, d->comm, *mesh);
-      if (d->damped) {
-        d->lsl.csr_vals = d->klvals.p;
-        d->lsu.csr_vals = d->kmvals.p;
-        halo_for(d->lsl, d->comm, *mesh);
-        halo_for(d->lsu, d->comm, *mesh);
-      }
-      for (auto* b : { &d->U, &d->V, &d->A, &d->MW }) {
-        b->alloc(d->n);
-        AFEM_HIP(hipMemsetAsync(b->p, 0, b->bytes(), ctx.stream));
-      }
-      d->W.alloc(d->n_cols);  // ghost part filled by the mass SpMV's halo exchange
-      AFEM_HIP(hipMemsetAsync(d->W.p, 0, d->W.bytes(), ctx.stream));
-      std::vector<int32_t> hn(n_fixed);
-      if (n_fixed) {
-        AFEM_HIP(hipMemcpyAsync(hn.data(), fixed_nodes, n_fixed * 4,
-                                mem == AFEM_MEM_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost, ctx.stream));
-        ctx.sync();
-      }
-      std::vector<int32_t> dofs;
-      for (int32_t nd : hn) {
-        AFEM_REQUIRE(nd >= 0 && nd < mesh->n_nodes, AFEM_ERR_ARG, "fixed node id out of range");
-        if (nd < mesh->n_own)
-          for (int i = 0; i < 3; ++i) dofs.push_back(3 * nd + i);
-      }
-      d->fixed.alloc(dofs.size());
-      if (!dofs.empty())
-        AFEM_HIP(hipMemcpyAsync(d->fixed.p, dofs.data(), dofs.size() * 4, hipMemcpyHostToDevice, ctx.stream));
-      ctx.sync();
+  const bool tri = mesh->nv == 3 && mesh->dim == 2;
+  AFEM_REQUIRE(tri || (mesh->nv == 4 && mesh->dim == 3), AFEM_ERR_NOT_IMPL,
+               "elastodynamics needs a tetrahedral (3D) or a triangle (2D) mesh");
+  AFEM_REQUIRE(prm->dt > 0 && prm->E > 0 && prm->nu > -1.0 && prm->nu < 0.5 && prm->rho >= 0, AFEM_ERR_ARG,
+               "elastodynamics: bad material or time step");
+  AFEM_REQUIRE(n_fixed == 0 || fixed_nodes, AFEM_ERR_ARG, "fixed_nodes is NULL");
+  AFEM_REQUIRE(prm->scheme == 0 || prm->scheme == 1, AFEM_ERR_ARG,
+               "elastodynamics: scheme 0 (Newmark-beta) or 1 (generalized-alpha)");
+  // each loop's own requirements on the communicator: here, before anything is allocated
+  if (tri) {
+    AFEM_REQUIRE(!comm || comm_nranks(comm) == 1, AFEM_ERR_NOT_IMPL,
+                 "2D elastodynamics runs on one subdomain (a communicator of more than one rank)");
+    AFEM_REQUIRE(mesh->n_own == mesh->n_nodes, AFEM_ERR_NOT_IMPL,
+                 "2D elastodynamics runs on one subdomain (the mesh has ghost nodes)");
+  }
+  else if (comm)
+    AFEM_REQUIRE(comm_nranks(comm) == 1 ||
+                     (mesh->st.valid && mesh->st.nranks == comm_nranks(comm) && mesh->st.rank == comm_rank(comm)) ||
+                     (mesh->part.valid && mesh->part.nranks == comm_nranks(comm) && mesh->part.rank == comm_rank(comm)),
+                 AFEM_ERR_ARG, "the mesh's slab / subdomain rank and nranks differ from the communicator");
+  mesh->ctx->set_device();
+  auto* d = new Elastodynamics();
+  try {
+    Ctx& ctx = *mesh->ctx;
+    d->mesh = mesh;
+    d->ctx = &ctx;
+    d->comm = comm;
+    d->p = *prm;
+    d->nb = tri ? 2 : 3;
+    if (!(d->p.penalty > 0)) d->p.penalty = 1.0e30;  // modules/elasticity/Fem.axl:37-41
+    // modules/elastodynamics/FemModule.cc:130-134, :239-240 (Lame; afem_elastodynamics_set_lame: :242-246)
+    // and :255-290 (time scheme)
+    d->mu2 = (prm->E / (2 * (1 + prm->nu))) * 2;
+    d->lambda = prm->E * prm->nu / ((1 + prm->nu) * (1 - 2 * prm->nu));
+    dyn_coefficients(d);
+    d->damped = prm->etak != 0.0 || (prm->scheme == 1 && prm->alpf != 0.0);
+    d->n = d->nb * mesh->n_own;
+    d->n_cols = d->nb * mesh->n_nodes;
+    // structure once; in 3D stiffness, mass and the damping operators share it
+    d->K.mesh = mesh;
+    d->K.nb_dof = d->nb;
+    d->K.order_per_block = false;  // CSR row order: the values are the linear system's matrix
+    build_structure(*mesh, d->K.s, tri ? 2 : 0);
+    d->K.values.alloc((size_t)d->K.s.nnz * d->nb * d->nb);
+    d->K.has_sparsity = true;
+    bsr_expand_scalar(d->K, nullptr);  // scalar rows / columns of the block CSR (shared by every operator)
+    init_ls(d->ls, &ctx, d->n, d->n_cols);
+    attach_csr(d->ls, d->K, d->K.values.p);
+    for (auto* b : { &d->U, &d->V, &d->A }) {
+      b->alloc(tri ? d->n_cols : d->n);
+      AFEM_HIP(hipMemsetAsync(b->p, 0, b->bytes(), ctx.stream));
     }
-    catch (...) {
-      delete d;
-      throw;
-    }
-    return d;
+    if (tri)
+      create_tri(d, fixed_nodes, n_fixed, mem);
+    else
+      create_tet(d, fixed_nodes, n_fixed, mem);
+  }
+  catch (...) {
+    delete d;
+    throw;
+  }
+  return d;
+}
+
+// ---------------------------------------------------------------- step
+namespace {
+void mark(const Elastodynamics* d, hipEvent_t e)
+{
+  if (d->profile) AFEM_HIP(hipEventRecord(e, d->ctx->stream));
+}
+
+// a double-couple DoF that a Dirichlet block constrains: the assignment would undo the condition's RHS
+void check_sources_tri(const Elastodynamics* d)
+{
+  for (const auto& dc : d->tri.dc2)
+    for (int32_t dof : dc.hdofs)
+      AFEM_REQUIRE(!d->tri.dir_dofs.count(dof), AFEM_ERR_ARG,
+                   "elastodynamics step: a double-couple DoF is constrained by a Dirichlet condition");
+}
+
+// LHS c0 M + K(c1, c2) and the body force (rhs = f |K|/4), re-assembled on the fixed structure
+void lhs_tet(Elastodynamics* d)
+{
+  const double f[3] = { d->p.body_force[0], d->p.body_force[1], d->p.body_force[2] };
+  assemble_elasticity_tet(d->K, d->c[1], d->c[2], d->c[0], f, d->ls.rhs.p, 0);
+}
+
+// LHS c0 M + K(c1, c2) and the whole RHS of :645-867 in one pass (set mode)
+void lhs_tri(Elastodynamics* d)
+{
+  const double f[2] = { d->p.body_force[0], d->p.body_force[1] };
+  assemble_elastodynamics_tri(d->K, d->c, f, d->U.p, d->V.p, d->A.p, d->tri.fixed2.p, d->ls.rhs.p, 0);
+}
+
+// rhs += op (a U + b V + c A)
+void rhs_add_tet(Elastodynamics* d, LinearSystem& op, double a, double b, double c)
+{
+  Ctx& ctx = *d->ctx;
+  vec_lincomb(ctx, d->n, a, d->U.p, b, d->V.p, c, d->A.p, d->tet.W.p);
+  ls_spmv(op, d->tet.W.p, d->tet.MW.p);
+  vec_lincomb(ctx, d->n, 1.0, d->ls.rhs.p, 1.0, d->tet.MW.p, 0.0, nullptr, d->ls.rhs.p);
+}
+
+void rhs_tet(Elastodynamics* d)
+{
+  const double* c = d->c;
+  rhs_add_tet(d, d->tet.lsm, c[0], c[3], c[4]);  // M (c0 U + c3 V + c4 A)
+  if (d->damped) {  // K(lambda = 1) (-c5 U + c7 V + c8 A) + K(2 mu = 1) (-c6 U + c9 V + c10 A)
+    rhs_add_tet(d, d->tet.lsl, -c[5], c[7], c[8]);
+    rhs_add_tet(d, d->tet.lsu, -c[6], c[9], c[10]);
   }
 }
 
+void rhs_tri(Elastodynamics* d)
+{
+  Ctx& ctx = *d->ctx;
+  const Elastodynamics::Tri& s = d->tri;
+  // paraxial boundaries (modules/soildynamics/FemModule.cc): the EDGE2 matrix added to the LHS
+  // (:1376-1486) and the edge loop over U, V, A to the RHS (:870-936), all blocks in one launch
+  if (s.par.n) {
+    const double rho = d->p.rho, dt = d->p.dt, gamma = d->gamma, beta = d->beta;
+    // the module's c7 .. c9 (:297-299) -- not the fused kernel's damping terms c[7 .. 10], zero here
+    const double p[3] = { rho * gamma / beta / dt, rho * (1. - gamma / beta), rho * dt * (1. - gamma / (2. * beta)) };
+    const double mu = 0.5 * d->mu2;  // wave speeds of E, nu or lambda, mu (:261-273) unless given (:275-278)
+    const double cs = s.cs > 0 ? s.cs : std::sqrt(mu / rho);
+    const double cp = s.cp > 0 ? s.cp : std::sqrt((d->lambda + 2. * mu) / rho);
+    paraxial_add(ctx, s.par, cp, cs, p, d->U.p, d->V.p, d->A.p, s.fixed2.p, d->K.values.p, d->ls.rhs.p);
+  }
+  // tractions t_i |e| / 2 per face node on the unfixed DoFs (:880-967), at the step's time for a table
+  for (const auto& tr : s.trac2) {
+    double t[2] = { tr.t[0], tr.t[1] };
+    if (!tr.times.empty()) table_interp(tr.times, tr.values, 2, s.t, t);
+    traction2_add(ctx, (int64_t)tr.nodes.n, tr.nodes.p, tr.w.p, t, tr.mask, s.fixed2.p, d->ls.rhs.p);
+  }
+}
+
+void constrain_tet(Elastodynamics* d)
+{
+  // clamped DoFs by penalty (the reference's default Dirichlet treatment)
+  if (d->tet.fixed.n)
+    ls_set_list(d->ls, d->tet.fixed.p, (int64_t)d->tet.fixed.n, AFEM_MEM_DEVICE, 0, 0.0, d->p.penalty);
+  // imposed displacements: diagonal = penalty, rhs = u penalty
+  // (modules/passmo/ElastodynamicModule.cc:1923-1939)
+  if (d->imp_ids.n)
+    ls_set_list(d->ls, d->imp_ids.p, (int64_t)d->imp_ids.n, AFEM_MEM_DEVICE, 0, 0.0, d->p.penalty, d->imp_vals.p);
+}
+
+// the deck's Dirichlet blocks in their order: later ones override earlier ones per DoF
+void constrain_tri(Elastodynamics* d)
+{
+  for (const auto& dc : d->tri.dir2)
+    ls_set_vectorial(d->ls, 2, dc.nodes.p, (int64_t)dc.nodes.n, AFEM_MEM_DEVICE, d->tri.dir_method, dc.v, dc.mask,
+                     d->p.penalty);
+}
+
+// double couple (modules/soildynamics/FemModule.cc:946-987): after everything else the listed DoFs'
+// RHS entries are ASSIGNED +-F, F = the source's table at the step's time
+void double_couple_tri(Elastodynamics* d)
+{
+  if (d->tri.dc2.empty()) return;
+  mark(d, d->tri.ev_dc[0]);  // timed apart: it belongs to rhs_ms, not to bc_ms
+  for (const auto& dc : d->tri.dc2) {
+    double F;
+    table_interp(dc.times, dc.values, 1, d->tri.t, &F);
+    vec_scatter_scaled(*d->ctx, (int64_t)dc.dofs.n, dc.dofs.p, dc.sign.p, F, d->ls.rhs.p);
+  }
+  mark(d, d->tri.ev_dc[1]);
+}
+
+void read_timing(Elastodynamics* d)
+{
+  float ms[5] = {};
+  for (int i = 0; i < 5; ++i) AFEM_HIP(hipEventElapsedTime(&ms[i], d->ev[i], d->ev[i + 1]));
+  float tot = 0.f, dc_ms = 0.f;
+  AFEM_HIP(hipEventElapsedTime(&tot, d->ev[0], d->ev[5]));
+  if (!d->tri.dc2.empty()) AFEM_HIP(hipEventElapsedTime(&dc_ms, d->tri.ev_dc[0], d->tri.ev_dc[1]));
+  afem_step_timing& t = d->timing;
+  t.assemble_ms = ms[0];
+  t.rhs_ms = ms[1] + dc_ms;  // 2D: the paraxial launch, the tractions and the double-couple assignment
+  t.bc_ms = ms[2] - dc_ms;
+  t.solve_ms = ms[3];
+  t.precond_ms = d->last.precond_ms;
+  t.update_ms = ms[4];
+  t.total_ms = tot;
+  t.iterations = d->last.iterations;
+}
+}  // namespace
+
 void dyn_step(Elastodynamics* d, afem_solve_stats* st)
 {
-  if (d->nb == 2) {
-    dyn_step_tri(d, st);
-    return;
-  }
-  {
-    Ctx& ctx = *d->ctx;
-    ctx.set_device();
-    const double f[3] = { d->p.body_force[0], d->p.body_force[1], d->p.body_force[2] };
-    const double* c = d->c;
-    const bool prof = d->profile;
-    auto mark = [&](int i) {
-      if (prof) AFEM_HIP(hipEventRecord(d->ev[i], ctx.stream));
-    };
-    ProfileCommGuard prof_guard(d->ls.opts, prof);  // the PCG times its preconditioner applications
-    mark(0);
-    // LHS c0 M + K(c1, c2) and the body force (rhs = f |K|/4), re-assembled on the fixed structure
-    assemble_elasticity_tet(d->K, c[1], c[2], c[0], f, d->ls.rhs.p, 0);
-    mark(1);
-    // rhs += M (c0 U + c3 V + c4 A)
-    vec_lincomb(ctx, d->n, c[0], d->U.p, c[3], d->V.p, c[4], d->A.p, d->W.p);
-    ls_spmv(d->lsm, d->W.p, d->MW.p);
-    vec_lincomb(ctx, d->n, 1.0, d->ls.rhs.p, 1.0, d->MW.p, 0.0, nullptr, d->ls.rhs.p);
-    if (d->damped) {  // rhs += K(lambda = 1) (-c5 U + c7 V + c8 A) + K(2 mu = 1) (-c6 U + c9 V + c10 A)
-      vec_lincomb(ctx, d->n, -c[5], d->U.p, c[7], d->V.p, c[8], d->A.p, d->W.p);
-      ls_spmv(d->lsl, d->W.p, d->MW.p);
-      vec_lincomb(ctx, d->n, 1.0, d->ls.rhs.p, 1.0, d->MW.p, 0.0, nullptr, d->ls.rhs.p);
-      vec_lincomb(ctx, d->n, -c[6], d->U.p, c[9], d->V.p, c[10], d->A.p, d->W.p);
-      ls_spmv(d->lsu, d->W.p, d->MW.p);
-      vec_lincomb(ctx, d->n, 1.0, d->ls.rhs.p, 1.0, d->MW.p, 0.0, nullptr, d->ls.rhs.p);
-    }
-    mark(2);
-    // clamped DoFs by penalty (the reference's default Dirichlet treatment)
-    if (d->fixed.n) ls_set_list(d->ls, d->fixed.p, (int64_t)d->fixed.n, AFEM_MEM_DEVICE, 0, 0.0, d->p.penalty);
-    // imposed displacements: diagonal = penalty, rhs = u penalty
-    // (modules/passmo/ElastodynamicModule.cc:1923-1939)
-    if (d->imp_ids.n)
-      ls_set_list(d->ls, d->imp_ids.p, (int64_t)d->imp_ids.n, AFEM_MEM_DEVICE, 0, 0.0, d->p.penalty, d->imp_vals.p);
-    // warm start from the Newmark predictor U + dt V + dt^2 (1/2 - beta) A
-    // (the PCG's stopping target is unchanged: the zero guess's residual)
-    vec_lincomb(ctx, d->n, 1.0, d->U.p, d->p.dt, d->V.p, d->p.dt * d->p.dt * (0.5 - d->beta), d->A.p, d->ls.sol.p);
-    d->ls.opts.initial_guess = 1;
-    mark(3);
-    ls_solve(d->ls, &d->last);
-    prof_guard.restore();
-    mark(4);
-    // the imposed values re-applied to the solution (_doSolve, :2369-2371)
-    if (d->imp_ids.n) vec_scatter(ctx, (int64_t)d->imp_ids.n, d->imp_ids.p, d->imp_vals.p, d->ls.sol.p);
-    newmark_update(ctx, d->n, d->p.dt, d->beta, d->gamma, d->ls.sol.p, d->U.p, d->V.p, d->A.p);
-    mark(5);
-    ctx.sync();
-    if (prof) {
-      float ms[5] = {};
-      for (int i = 0; i < 5; ++i) AFEM_HIP(hipEventElapsedTime(&ms[i], d->ev[i], d->ev[i + 1]));
-      float tot = 0.f;
-      AFEM_HIP(hipEventElapsedTime(&tot, d->ev[0], d->ev[5]));
-      afem_step_timing& t = d->timing;
-      t.assemble_ms = ms[0];
-      t.rhs_ms = ms[1];
-      t.bc_ms = ms[2];
-      t.solve_ms = ms[3];
-      t.precond_ms = d->last.precond_ms;
-      t.update_ms = ms[4];
-      t.total_ms = tot;
-      t.iterations = d->last.iterations;
-    }
-    if (st) *st = d->last;
-  }
+  Ctx& ctx = *d->ctx;
+  ctx.set_device();
+  const bool tri = d->nb == 2;
+  if (tri) check_sources_tri(d);
+  ProfileCommGuard prof_guard(d->ls.opts, d->profile);  // the PCG times its preconditioner applications
+  mark(d, d->ev[0]);
+  if (tri)
+    lhs_tri(d);
+  else
+    lhs_tet(d);
+  mark(d, d->ev[1]);
+  if (tri)
+    rhs_tri(d);
+  else
+    rhs_tet(d);
+  mark(d, d->ev[2]);
+  if (tri)
+    constrain_tri(d);
+  else
+    constrain_tet(d);
+  // warm start from the Newmark predictor U + dt V + dt^2 (1/2 - beta) A
+  // (the PCG's stopping target is unchanged: the zero guess's residual)
+  vec_lincomb(ctx, d->n, 1.0, d->U.p, d->p.dt, d->V.p, d->p.dt * d->p.dt * (0.5 - d->beta), d->A.p, d->ls.sol.p);
+  d->ls.opts.initial_guess = 1;
+  if (tri) double_couple_tri(d);
+  mark(d, d->ev[3]);
+  ls_solve(d->ls, &d->last);
+  prof_guard.restore();
+  mark(d, d->ev[4]);
+  // the constrained / imposed values re-applied to the solution (2D: _solve, :1416-1417; passmo: _doSolve, :2369-2371)
+  if (d->imp_ids.n) vec_scatter(ctx, (int64_t)d->imp_ids.n, d->imp_ids.p, d->imp_vals.p, d->ls.sol.p);
+  newmark_update(ctx, d->n, d->p.dt, d->beta, d->gamma, d->ls.sol.p, d->U.p, d->V.p, d->A.p);
+  mark(d, d->ev[5]);
+  ctx.sync();
+  if (tri) d->tri.t += d->p.dt;  // _updateTime, :189
+  if (d->profile) read_timing(d);
+  if (st) *st = d->last;
 }
 
 void dyn_set_dirichlet(Elastodynamics* d, const int32_t* dofs, const double* values, int64_t n, int mem)
@@ -808,14 +761,8 @@ void dyn_set_dirichlet(Elastodynamics* d, const int32_t* dofs, const double* val
                "afem_elastodynamics_set_dirichlet is the 3D loop's entry (2D: afem_elastodynamics_set_dirichlet_vectorial)");
   Ctx& ctx = *d->ctx;
   ctx.set_device();
-  std::vector<int32_t> hd(n);
-  std::vector<double> hv(n);
-  if (n) {
-    const hipMemcpyKind k = mem == AFEM_MEM_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost;
-    AFEM_HIP(hipMemcpyAsync(hd.data(), dofs, n * sizeof(int32_t), k, ctx.stream));
-    AFEM_HIP(hipMemcpyAsync(hv.data(), values, n * sizeof(double), k, ctx.stream));
-    ctx.sync();
-  }
+  const std::vector<int32_t> hd = to_host(ctx, dofs, n, mem);
+  const std::vector<double> hv = to_host(ctx, values, n, mem);
   // owned DoFs only (the reference loops over ownNodes(), :1923); the last
   // value of a DoF listed twice wins, as the module's successive conditions
   std::map<int32_t, double> m;
@@ -829,13 +776,8 @@ void dyn_set_dirichlet(Elastodynamics* d, const int32_t* dofs, const double* val
     ids.push_back(kv.first);
     vals.push_back(kv.second);
   }
-  d->imp_ids.alloc(ids.size());
-  d->imp_vals.alloc(vals.size());
-  if (!ids.empty()) {
-    AFEM_HIP(hipMemcpyAsync(d->imp_ids.p, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, ctx.stream));
-    AFEM_HIP(hipMemcpyAsync(d->imp_vals.p, vals.data(), vals.size() * 8, hipMemcpyHostToDevice, ctx.stream));
-  }
-  ctx.sync();
+  upload(ctx, d->imp_ids, ids);
+  upload(ctx, d->imp_vals, vals);
 }
 
 void dyn_set_time_step(Elastodynamics* d, double dt)
@@ -855,7 +797,8 @@ void dyn_profile(Elastodynamics* d, bool on)
   d->ctx->set_device();
   if (on && !d->ev[0]) {
     for (auto& e : d->ev) AFEM_HIP(hipEventCreate(&e));
-    for (auto& e : d->ev_dc) AFEM_HIP(hipEventCreate(&e));
+    if (d->nb == 2)
+      for (auto& e : d->tri.ev_dc) AFEM_HIP(hipEventCreate(&e));
   }
   d->profile = on;
   afem_step_timing& t = d->timing;
@@ -872,11 +815,15 @@ void dyn_destroy(Elastodynamics* d)
   (void)hipStreamSynchronize(d->ctx->stream);
   for (auto& e : d->ev)
     if (e) (void)hipEventDestroy(e);
-  for (auto& e : d->ev_dc)
-    if (e) (void)hipEventDestroy(e);
   if (d->ls.pinned) (void)hipHostFree(d->ls.pinned);
-  for (LinearSystem* l : { &d->lsm, &d->lsl, &d->lsu })
-    if (l->pinned) (void)hipHostFree(l->pinned);
+  if (d->nb == 2) {
+    for (auto& e : d->tri.ev_dc)
+      if (e) (void)hipEventDestroy(e);
+  }
+  else {
+    for (LinearSystem* l : { &d->tet.lsm, &d->tet.lsl, &d->tet.lsu })
+      if (l->pinned) (void)hipHostFree(l->pinned);
+  }
   delete d;
 }
 

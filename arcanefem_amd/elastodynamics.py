@@ -16,16 +16,6 @@ restates the reference's time-stepping callers of the linear-system path:
   re-assembled every step (:149-153).
 * ``modules/passmo/ElastodynamicModule.cc`` (3D): re-assembly every step on a
   fixed structure (:469-536).
-
-Here the same scheme runs in 3D on P1 tetrahedra with block-3 BSR, on one
-subdomain or on one ghosted z-slab per rank (``comm``: RCCL ``Communicator`` or
-``parallel.HostCommunicator``): each step re-assembles ``c0 M + K`` and the
-body-force RHS in one fused HIP kernel on the fixed sparsity, adds
-``M (c0 U + c3 V + c4 A)`` (the mass operator shares the structure; its SpMV
-exchanges the ghost values of the operand), clamps the fixed nodes by
-penalty, solves with the PCG (3x3 node-block Jacobi by default, warm started
-from the Newmark predictor; halo + all-reduces over the ranks) and
-applies the Newmark update on the device.
 """
 from __future__ import annotations
 
@@ -61,39 +51,29 @@ def young_from_lame(lam: float, mu: float):
     return 2.0 * mu * (1.0 + nu), nu
 
 
-class Elastodynamics3D:
-    def __init__(self, ctx: Context, mesh: Mesh, E: float, nu: float, rho: float, dt: float,
-                 body_force=(0.0, 0.0, 0.0), fixed_nodes=None, penalty: float = 1.0e30, rtol: float = 1e-12,
-                 comm=None, max_iter: int = 20000, preconditioner: str = "jacobi", etam: float = 0.0,
-                 etak: float = 0.0, alpm: float = 0.0, alpf: float = 0.0, time_discretization: str = "newmark-beta"):
-        """time_discretization, etam, etak, alpm, alpf: the module's
-        timeDiscretization and damping options (Fem.axl of
-        modules/elastodynamics; FemModule.cc:222-296)."""
-        if mesh.dim != 3:
-            raise ValueError("Elastodynamics3D needs a tetrahedral mesh")
+class _Elastodynamics:
+    """The native handle and what both loops do with it; a subclass gives NB (DoFs per node) and MESH (dim, word)."""
+
+    def _check(self, mesh: Mesh, time_discretization: str):
+        if mesh.dim != self.MESH[0]:
+            raise ValueError(f"{type(self).__name__} needs a {self.MESH[1]} mesh")
         if time_discretization.lower() not in SCHEMES:
             raise ValueError("Only Newmark-beta | Generalized-alpha are supported for time-discretization")
-        self.ctx, self.mesh, self.dt = ctx, mesh, dt
-        self.n = 3 * mesh.n_own_nodes
+
+    def _open(self, ctx, mesh, E, nu, rho, dt, body_force, penalty, etam, etak, alpm, alpf, time_discretization,
+              comm, fixed_nodes, opts, t0):
+        """Fills NewmarkParams, creates the handle and sets the solver options; t0: the time of the first step."""
+        self.ctx, self.mesh, self.dt, self.t = ctx, mesh, dt, t0
+        self.n = self.NB * mesh.n_own_nodes
+        self.last_stats = None
         p = C.NewmarkParams(E, nu, rho, dt, (ctypes.c_double * 3)(*[float(x) for x in body_force]), penalty, 0.0, 0.0,
                             etam, etak, alpm, alpf, SCHEMES[time_discretization.lower()], 0)
-        fixed = np.zeros(0, dtype=np.int32) if fixed_nodes is None else np.ascontiguousarray(fixed_nodes,
-                                                                                            dtype=np.int32)
-        h = ctypes.c_void_p()
+        fixed = np.ascontiguousarray([] if fixed_nodes is None else fixed_nodes, dtype=np.int32)
+        self.h = ctypes.c_void_p()
         call("afem_elastodynamics_create", mesh.h, comm.h if comm is not None else None, ctypes.byref(p),
              ctypes.c_void_p(fixed.ctypes.data) if fixed.size else None, fixed.size, C.AFEM_MEM_HOST,
-             ctypes.byref(h))
-        self.h = h
-        # "multigrid": the geometric multigrid V-cycle on structured boxes (one rank or z-slabs), built at
-        # the first step and reused (the Newmark operator c0 M + K is the same every step)
-        # "amg-reuse": the algebraic multigrid (any mesh; rebuilt when dt changes the operator)
-        blk, mgm, amg = {"jacobi": (0, 0, 0), "block3": (3, 0, 0), "multigrid": (0, 2, 0),
-                         "amg-reuse": (0, 0, 2)}[preconditioner]
-        o = C.SolverOpts(C.AFEM_SOLVER_PCG, max_iter, rtol, 0.0, 8, 0, 0, blk, mgm)
-        o.amg = amg
-        call("afem_elastodynamics_set_solver_options", self.h, ctypes.byref(o))
-        self.t = 0.0
-        self.last_stats = None
+             ctypes.byref(self.h))
+        call("afem_elastodynamics_set_solver_options", self.h, ctypes.byref(opts))
 
     def step(self) -> dict:
         st = C.SolveStats()
@@ -103,16 +83,6 @@ class Elastodynamics3D:
                                residual_norm=st.residual_norm, solve_ms=st.solve_ms, amg_levels=st.amg_levels,
                                amg_setup_ms=st.amg_setup_ms, precond_ms=st.precond_ms)
         return self.last_stats
-
-    def setDirichlet(self, dofs, values):
-        """Imposed displacements by penalty (passmo's dirichlet-surface /
-        point conditions, modules/passmo/ElastodynamicModule.cc:1923-1939 and
-        the re-application after the solve :2369-2371): local DoF ids
-        (3 node + component) and their values; replaces the previous list."""
-        d = np.ascontiguousarray(dofs, dtype=np.int32).ravel()
-        v = np.ascontiguousarray(np.broadcast_to(np.asarray(values, dtype=np.float64), d.shape))
-        call("afem_elastodynamics_set_dirichlet", self.h, ctypes.c_void_p(d.ctypes.data) if d.size else None,
-             ctypes.c_void_p(v.ctypes.data) if v.size else None, d.size, C.AFEM_MEM_HOST)
 
     def setTimeStep(self, dt: float):
         """dt from the next step on (passmo's shortened final step, :525-530)."""
@@ -154,6 +124,47 @@ class Elastodynamics3D:
             self.h = None
 
 
+class Elastodynamics3D(_Elastodynamics):
+    """The same scheme in 3D on P1 tetrahedra with block-3 BSR, on one
+    subdomain or on one ghosted z-slab per rank (``comm``: RCCL ``Communicator`` or
+    ``parallel.HostCommunicator``): each step re-assembles ``c0 M + K`` and the
+    body-force RHS in one fused HIP kernel on the fixed sparsity, adds
+    ``M (c0 U + c3 V + c4 A)`` (the mass operator shares the structure; its SpMV
+    exchanges the ghost values of the operand), clamps the fixed nodes by
+    penalty, solves with the PCG (Jacobi by default, warm started from the
+    Newmark predictor; halo + all-reduces over the ranks) and applies the
+    Newmark update on the device.  The handle and the step are the base's."""
+    NB, MESH = 3, (3, "tetrahedral")
+
+    def __init__(self, ctx: Context, mesh: Mesh, E: float, nu: float, rho: float, dt: float,
+                 body_force=(0.0, 0.0, 0.0), fixed_nodes=None, penalty: float = 1.0e30, rtol: float = 1e-12,
+                 comm=None, max_iter: int = 20000, preconditioner: str = "jacobi", etam: float = 0.0,
+                 etak: float = 0.0, alpm: float = 0.0, alpf: float = 0.0, time_discretization: str = "newmark-beta"):
+        """time_discretization, etam, etak, alpm, alpf: the module's
+        timeDiscretization and damping options (Fem.axl of
+        modules/elastodynamics; FemModule.cc:222-296)."""
+        self._check(mesh, time_discretization)
+        # "multigrid": the geometric multigrid V-cycle on structured boxes (one rank or z-slabs), built at
+        # the first step and reused (the Newmark operator c0 M + K is the same every step)
+        # "amg-reuse": the algebraic multigrid (any mesh; rebuilt when dt changes the operator)
+        blk, mgm, amg = {"jacobi": (0, 0, 0), "block3": (3, 0, 0), "multigrid": (0, 2, 0),
+                         "amg-reuse": (0, 0, 2)}[preconditioner]
+        o = C.SolverOpts(C.AFEM_SOLVER_PCG, max_iter, rtol, 0.0, 8, 0, 0, blk, mgm)
+        o.amg = amg
+        self._open(ctx, mesh, E, nu, rho, dt, body_force, penalty, etam, etak, alpm, alpf, time_discretization, comm,
+                   fixed_nodes, o, 0.0)
+
+    def setDirichlet(self, dofs, values):
+        """Imposed displacements by penalty (passmo's dirichlet-surface /
+        point conditions, modules/passmo/ElastodynamicModule.cc:1923-1939 and
+        the re-application after the solve :2369-2371): local DoF ids
+        (3 node + component) and their values; replaces the previous list."""
+        d = np.ascontiguousarray(dofs, dtype=np.int32).ravel()
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(values, dtype=np.float64), d.shape))
+        call("afem_elastodynamics_set_dirichlet", self.h, ctypes.c_void_p(d.ctypes.data) if d.size else None,
+             ctypes.c_void_p(v.ctypes.data) if v.size else None, d.size, C.AFEM_MEM_HOST)
+
+
 DIRICHLET_METHODS = {"penalty": C.AFEM_DIRICHLET_PENALTY, "rowelimination": C.AFEM_DIRICHLET_ROW_ELIMINATION,
                      "rowcolumnelimination": C.AFEM_DIRICHLET_ROW_COLUMN_ELIMINATION, "weakpenalty": -1}
 
@@ -166,7 +177,7 @@ def _mask_values(x):
             (ctypes.c_double * 2)(*[0.0 if c is None else float(c) for c in x]))
 
 
-class Elastodynamics2D(Elastodynamics3D):
+class Elastodynamics2D(_Elastodynamics):
     """The module modules/elastodynamics itself: TRIA3, block 2, one subdomain.
 
     Each step is one fused HIP kernel for the LHS c0 M + K(c1, c2) and the
@@ -180,6 +191,7 @@ class Elastodynamics2D(Elastodynamics3D):
     "RowElimination" or "RowColumnElimination" (the stated value is imposed;
     "WeakPenalty" is not implemented).
     """
+    NB, MESH = 2, (2, "triangle")
 
     def __init__(self, ctx: Context, mesh: Mesh, rho: float, dt: float, lam: float | None = None,
                  mu: float | None = None, E: float | None = None, nu: float | None = None, body_force=(None, None),
@@ -187,10 +199,7 @@ class Elastodynamics2D(Elastodynamics3D):
                  time_discretization: str = "newmark-beta", enforce_dirichlet_method: str = "Penalty",
                  penalty: float = 1.0e30, rtol: float = 1e-12, max_iter: int = 20000, solver: str = "pcg",
                  preconditioner: str = "jacobi", comm=None):
-        if mesh.dim != 2:
-            raise ValueError("Elastodynamics2D needs a triangle mesh")
-        if time_discretization.lower() not in SCHEMES:
-            raise ValueError("Only Newmark-beta | Generalized-alpha are supported for time-discretization")
+        self._check(mesh, time_discretization)
         if preconditioner != "jacobi":
             raise ValueError("Elastodynamics2D solves with the Jacobi-PCG or the direct solver "
                              f"(preconditioner {preconditioner!r} is the 3D loop's)")
@@ -201,17 +210,14 @@ class Elastodynamics2D(Elastodynamics3D):
         if (lam is None) != (mu is None) or (E is None) != (nu is None) or (lam is None) == (E is None):
             raise ValueError("give the material as lam and mu, or as E and nu")
         self.method = DIRICHLET_METHODS[method]
-        self.ctx, self.mesh, self.dt = ctx, mesh, dt
-        self.n = 2 * mesh.n_own_nodes
         if lam is not None:
             E, nu = young_from_lame(lam, mu)
-        mask, f = _mask_values(body_force)
-        p = C.NewmarkParams(E, nu, rho, dt, (ctypes.c_double * 3)(f[0], f[1], 0.0), penalty, 0.0, 0.0, etam, etak, alpm,
-                            alpf, SCHEMES[time_discretization.lower()], 0)
-        h = ctypes.c_void_p()
-        call("afem_elastodynamics_create", mesh.h, comm.h if comm is not None else None, ctypes.byref(p), None, 0,
-             C.AFEM_MEM_HOST, ctypes.byref(h))
-        self.h = h
+        _, f = _mask_values(body_force)
+        o = C.SolverOpts({"auto": C.AFEM_SOLVER_AUTO, "pcg": C.AFEM_SOLVER_PCG, "direct": C.AFEM_SOLVER_DIRECT}[solver],
+                         max_iter, rtol, 0.0, 8, 0, 0, 0, 0)
+        self._open(ctx, mesh, E, nu, rho, dt, (f[0], f[1], 0.0), penalty, etam, etak, alpm, alpf, time_discretization,
+                   comm, None, o, dt)  # t0 = dt: the time of the next step (FemModule.cc:175)
+        self.n_tractions = 0
         try:
             if lam is not None:
                 call("afem_elastodynamics_set_lame", self.h, float(lam), float(mu))
@@ -220,12 +226,6 @@ class Elastodynamics2D(Elastodynamics3D):
         except Exception:
             self.close()
             raise
-        o = C.SolverOpts({"auto": C.AFEM_SOLVER_AUTO, "pcg": C.AFEM_SOLVER_PCG, "direct": C.AFEM_SOLVER_DIRECT}[solver],
-                         max_iter, rtol, 0.0, 8, 0, 0, 0, 0)
-        call("afem_elastodynamics_set_solver_options", self.h, ctypes.byref(o))
-        self.t = dt  # the time of the next step (FemModule.cc:175)
-        self.n_tractions = 0
-        self.last_stats = None
 
     def setDirichlet(self, nodes, u):
         """One dirichlet-boundary-condition / dirichlet-point-condition block:
@@ -282,10 +282,7 @@ class Soildynamics2D(Elastodynamics2D):
                  cs: float | None = None, lam: float | None = None, mu: float | None = None, E: float | None = None,
                  nu: float | None = None, body_force=(None, None), time_discretization: str = "newmark-beta",
                  alpm: float = 0.0, alpf: float = 0.0, **kw):
-        if mesh.dim != 2:
-            raise ValueError("Soildynamics2D needs a triangle mesh")
-        if time_discretization.lower() not in SCHEMES:
-            raise ValueError("Only Newmark-beta | Generalized-alpha are supported for time-discretization")
+        self._check(mesh, time_discretization)
         if SCHEMES[time_discretization.lower()] != 0:
             raise ValueError("Only Newmark-beta works for time-discretization Generalized-alpha WIP")
         pairs = [(cp, cs), (lam, mu), (E, nu)]
